@@ -3,6 +3,13 @@
 the faiss-semantics CPU restatement), N=10M d=1536 bf16, batch=256, top-100 (BASELINE cfg3).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg1|cfg2|cfg4|cfg5]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs: it builds the corpus, warms up, times the K steps,
+writes the last timed step's results under --dump-outputs DIR (if given) and prints the JSON line
+(the roofline figures in it come from the library's HIP events of those same K steps).  --full adds
+every leg that takes runs of its own: the other screen / scan / query-tile mode timed beside, the
+host-enqueue and power-pair probes, the exact ground truth and recall, the CPU baseline and parity.
 
 One process per GPU: under torchrun (WORLD_SIZE set, which must equal --gpus), or -- when
 --gpus N > 1 is given without a launcher -- this process spawns N fresh child processes with
@@ -12,7 +19,7 @@ oracle/vs_oracle.c); every rank holds the same synthetic query batch.  One step 
 one batch: per-shard exact search (pack -> MFMA screen with fused top-k -> merge -> exact
 refine) and, for N > 1, an RCCL all-gather of the per-shard (fp64 score, id) lists + the on-device
 merge (photo_search_engine_amd/distributed.py, the product's multi-GPU layer).  Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP events on its own
-stream) and `cpu_baseline` (faiss fp32 restatement on this host, bounded sample).
+stream) and, with --full, `cpu_baseline` (faiss fp32 restatement on this host, bounded sample).
 """
 from __future__ import annotations
 
@@ -60,6 +67,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WORKLOADS) + sorted(IVF_WORKLOADS) + ["cfg1"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: the other screen / scan / query-tile mode "
+                         "timed beside, host-enqueue and power-pair probes, ground truth and recall, CPU baseline "
+                         "and parity (a plain run only sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 scores, ids and canonical scores as float64)")
     ap.add_argument("--rows", type=int, default=0, help="override corpus rows (testing)")
     ap.add_argument("--shard-of", type=int, default=0,
                     help="measure ONE rank of a G-shard step on this GPU: its N/G-row shard, the two-phase "
@@ -71,21 +85,21 @@ def parse():
                          "reference's metric='l2' stores, utils/vector_store.py:79-81)")
     ap.add_argument("--screen", default=None, choices=["native", "int8"],
                     help="flat workloads: the screen of the timed steps (default: int8); "
-                         "with int8 the native screen is timed too and reported beside it")
+                         "with int8, --full times the native screen too and reports it beside")
     ap.add_argument("--cpu-sample-rows", type=int, default=0,
                     help="rows of the corpus the CPU baseline scans (default: the whole corpus if host memory allows)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal only: every rank on cuda:0 (with --dist-backend gloo on a 1-GPU box)")
-    ap.add_argument("--no-recall", action="store_true", help="cfg5: skip the exact ground truth (profiling runs)")
+    ap.add_argument("--no-recall", action="store_true", help="cfg5 --full: skip the exact ground truth")
     ap.add_argument("--skew", type=float, default=0.0,
                     help="cfg5: Zipf exponent of the cluster sizes (0 = equal-sized clusters; 1.1 = a heavy head)")
     ap.add_argument("--ivf-qtile", default="split", choices=["plain", "split"],
-                    help="cfg5: query tiles of the MFMA list scans' first pass (the other mode runs beside)")
+                    help="cfg5: query tiles of the MFMA list scans' first pass (--full runs the other mode beside)")
     ap.add_argument("--ivf-scan", default="auto", choices=["auto", "gemv", "mfma"],
                     help="cfg5: list-scan kernels (auto: MFMA screen for lists probed by many queries; "
-                         "with auto the GEMV-only scan is timed too and reported beside it)")
+                         "with auto, --full times the GEMV-only scan too and reports it beside)")
     ap.add_argument("--data", default="iso", choices=["iso", "mixture", "mixture-sorted"],
                     help="flat workloads: isotropic rows (default, the BASELINE data), or a Gaussian mixture "
                          "(64 clusters, sigma --sigma) in random / cluster-sorted insertion order; the "
@@ -233,6 +247,7 @@ def main():
         sh.floor_override = _shard_floor(args, N, d, dtype, nq, k, q, local, dev, torch)
     t_build = time.time() - t_build
     result = {}
+    last = {}
     per_rank = {}
     host_ms = {}
     host_in_loop = {}
@@ -273,16 +288,18 @@ def main():
         sh.exchange_timing = False
         km, kd = ix.timing_fetch()
         xm = sh.exchange_times_fetch()
-        # host time to enqueue one step with the device idle (untimed diagnostic: a step whose host
-        # side exceeds its device time leaves the device waiting on the host)
-        hs = []
-        for _ in range(3):
+        last[scr] = {k_: v.clone() for k_, v in result.items()}  # what the last timed step returned
+        if args.full:
+            # host time to enqueue one step with the device idle (untimed diagnostic: a step whose host
+            # side exceeds its device time leaves the device waiting on the host)
+            hs = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                th = time.perf_counter()
+                step()
+                hs.append((time.perf_counter() - th) * 1e3)
             torch.cuda.synchronize()
-            th = time.perf_counter()
-            step()
-            hs.append((time.perf_counter() - th) * 1e3)
-        torch.cuda.synchronize()
-        host_ms[scr] = float(np.median(hs))
+            host_ms[scr] = float(np.median(hs))
         host_in_loop[scr] = t_in * 1e3 / max(args.steps, 1)
         per_rank[scr] = [float(np.mean(km)) if km else float("nan"), sum(xm) / args.steps, len(xm) / args.steps,
                          el * 1e3 / args.steps, float(n_local)]
@@ -297,9 +314,9 @@ def main():
 
     es = 2 if dtype in ("bf16", "f16") else 4
     alt = None
-    if screen == "int8":  # the native (bf16 MFMA) screen of the same corpus, reported beside it
+    if screen == "int8" and args.full:  # the native (bf16 MFMA) screen of the same corpus, reported beside it
         el_n, km_n, kind_n, unc_n, _ = timed("native")
-        res_native = {k_: v.clone() for k_, v in result.items()}
+        res_native = last.pop("native")
         kn = float(np.mean(km_n)) if km_n else float("nan")
         bytes_n = n_local * d * es + nq * d * es + nq * k * 12 + (n_local * 4 if args.metric == "l2" else 0)
         alt = {"screen": "native", "kernel": _kernel_name(kind_n, dtype, d), "value": round(nq * args.steps / el_n, 2),
@@ -345,6 +362,11 @@ def main():
     traffic = _traffic(args.traffic_file, args.workload, n_local, kind)
 
     out = None
+    if rank == 0 and args.full:
+        # the same box's zero / real operand pair of the main screen kernels (vs_screen_probe)
+        power_pair = _power_pair(ix, q, nq, kind, alg_bytes,
+                                 n_local * d * es + nq * d * es + nq * k * 12 + (n_local * 4 if args.metric == "l2" else 0),
+                                 torch.cuda.current_stream(dev).cuda_stream)
     if rank == 0:
         out = {
             # a --rows run is a different configuration: its metric names the rows it ran on
@@ -361,7 +383,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4),
-            "host_enqueue_ms": round(host_ms.get(screen, float("nan")), 4),
             "host_ms_in_loop": round(host_in_loop.get(screen, float("nan")), 4),
             "higher_is_better": True,
             "scaling": "strong",
@@ -394,11 +415,6 @@ def main():
                 "mfma_tflops": round(alg_flops / (kavg * 1e-3) / 1e12, 1),
                 "mfma_frac": round(alg_flops / (kavg * 1e-3) / 1e12 / peak_flops, 4),
                 "mfma_peak_tflops": peak_flops,
-                # the same box's zero / real operand pair of the main screen kernels (vs_screen_probe)
-                "power_pair": _power_pair(ix, q, nq, kind, alg_bytes,
-                                          n_local * d * es + nq * d * es + nq * k * 12 +
-                                          (n_local * 4 if args.metric == "l2" else 0),
-                                          torch.cuda.current_stream(dev).cuda_stream),
             },
             # first-pass certificate failures; every one was re-searched exactly (search_device_exact)
             "uncertified_first_pass": uncert,
@@ -407,6 +423,9 @@ def main():
             "screen_state": ix.screen_state(),
             "build_s": round(t_build, 2),
         }
+        if args.full:
+            out["host_enqueue_ms"] = round(host_ms.get(screen, float("nan")), 4)
+            out["roofline"]["power_pair"] = power_pair
         if G > 1 or args.shard_of > 1:
             # per rank: its dominant kernel's mean ms (HIP events in the library), the all-gathers'
             # ms per step (HIP events around each collective on the calling stream) and its wall ms
@@ -419,7 +438,10 @@ def main():
                                         "(allocated capacity)"}
         if alt is not None:
             out["native_screen"] = alt
-    if rank == 0 and G == 1 and not args.no_cpu_baseline and args.data == "iso" and args.metric == "ip" and not args.shard_of:
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(args.dump_outputs, {k_: v.cpu().numpy() for k_, v in last[screen].items()})
+    if (rank == 0 and args.full and G == 1 and not args.no_cpu_baseline and args.data == "iso" and args.metric == "ip"
+            and not args.shard_of):
         out["cpu_baseline"], out["recall@10"], out["parity"] = cpu_baseline_and_recall(
             args, N, d, dtype, nq, k, local, torch, (result["D"].cpu().numpy(), result["I"].cpu().numpy()))
     if rank == 0:
@@ -427,6 +449,25 @@ def main():
     sh.close()
     if G > 1 or args.shard_of > 1:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def _dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: write each returned array as ``path/<name>.npy``.  float32 / float64 arrays
+    keep their type, ids go out as float64 (exact below 2^53).  All files together stay within
+    DUMP_BUDGET_BYTES: an array above its equal share is cut to a fixed, seeded sample of its
+    leading axis (sorted, so two builds write the same rows in the same order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(int(share // max(a.nbytes // a.shape[0], 1)), 1)
+            rows = np.sort(np.random.default_rng(20260420).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def _power_pair(ix, q, nq: int, kind: str, alg_bytes: int, alg_bytes_native: int, stream: int) -> dict:
@@ -738,7 +779,10 @@ def run_cfg1(args):
                         "kernel_ms": round(kavg, 4), "alg_bytes_per_launch": alg_bytes,
                         "note": "61 MB per call is a few microseconds of HBM: the call is launch/latency-bound"},
            "build_s": round(t_build, 2)}
-    if not args.no_cpu_baseline:
+    if args.dump_outputs and got:  # the last timed call's result dicts, as (distance, row id) arrays
+        _dump_outputs(args.dump_outputs, {"D": np.array([r["distance"] for r in got[-1]], dtype=np.float32),
+                                          "I": np.array([r["metadata"]["row"] for r in got[-1]], dtype=np.int64)})
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         xn = np.stack([np.asarray(O.np_normalize_like_reference(r), dtype=np.float32) for r in x])
         qn = np.stack([np.asarray(O.np_normalize_like_reference(r), dtype=np.float32) for r in qs])
@@ -846,8 +890,10 @@ def run_ivf(args):
     sizes = ix.list_sizes()
     Ig = I.cpu().numpy()
     mfma_lists, uncert, mfma_bytes, gemv_bytes = ix.last_search_detail()
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, {"D": D.cpu().numpy(), "I": Ig, "S": S.cpu().numpy()})
     gemv_beside = None
-    if args.ivf_scan == "auto" and mfma_lists > 0:  # the GEMV-only scan on the same batch, beside
+    if args.full and args.ivf_scan == "auto" and mfma_lists > 0:  # the GEMV-only scan on the same batch, beside
         Sg0 = S.cpu().numpy()
         ix.set_scan("gemv")
         step()
@@ -866,7 +912,7 @@ def run_ivf(args):
                                                  np.array_equal(S.cpu().numpy(), Sg0))}
         ix.set_scan(args.ivf_scan)
     qtile_beside = None
-    if mfma_lists > 0:  # the other query-tile mode of the MFMA list scans on the same batch, beside
+    if args.full and mfma_lists > 0:  # the other query-tile mode of the MFMA list scans on the same batch, beside
         Sg0 = S.cpu().numpy()
         other = "split" if args.ivf_qtile == "plain" else "plain"
         ix.set_query_tiles(other)
@@ -888,16 +934,19 @@ def run_ivf(args):
         ix.set_query_tiles(args.ivf_qtile)
 
     # probes (exact coarse top-nprobe) and per-batch scan volume, for the CPU baseline
-    cf = FlatIndex(d, "ip", dtype, device=0)
-    cf.add(ix.centroids())
     qh = q.cpu().numpy()
-    _, P = cf.search(qh, nprobe)
-    cf.close()
-    pairs = float(sum(int(sizes[l]) for l in P.reshape(-1)))  # (row, query) dot products per batch
+    P, pairs = None, 0.0
+    if args.full:
+        cf = FlatIndex(d, "ip", dtype, device=0)
+        cf.add(ix.centroids())
+        _, P = cf.search(qh, nprobe)
+        cf.close()
+        pairs = float(sum(int(sizes[l]) for l in P.reshape(-1)))  # (row, query) dot products per batch
 
     # exact flat ground truth over the whole corpus, shard by shard (the IVF stays resident)
-    shard = 6_250_000 if not args.no_recall else N + 1
-    if args.no_recall:
+    no_recall = args.no_recall or not args.full
+    shard = 6_250_000 if not no_recall else N + 1
+    if no_recall:
         N_gt = 0
     else:
         N_gt = N
@@ -940,7 +989,7 @@ def run_ivf(args):
                 need += 1
                 got += int(i in res)
 
-    if os.environ.get("VS_IVF_DEBUG"):
+    if os.environ.get("VS_IVF_DEBUG") and parts_S:
         Sg = S.cpu().numpy()
         for a in [a for a in range(nq) if set(Ig[a, :10].tolist()) != set(Itrue[a, :10].tolist())][:3]:
             _progress(f"q{a} ivf  {Ig[a, :10].tolist()} {np.round(Sg[a, :10], 6).tolist()}")
@@ -993,7 +1042,7 @@ def run_ivf(args):
         "recall@10": round(hit / (nq * 10.0), 6) if parts_S else None,
         "probed_recall@10": round(got / max(need, 1), 6) if parts_S else None,
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = ivf_cpu_baseline(d, dtype, qh, k, pairs, ix.centroids(), nprobe)
     print(json.dumps(out), flush=True)
     ix.close()
