@@ -236,6 +236,44 @@ int64_t vs_screen_copy_bytes(vs_index* index);
 #define VS_SCREEN_STATE_N 9
 int vs_screen_state(vs_index* index, double* out, int cap);
 
+/* ==== id selectors: exact filtered search on the flat index =================================
+ * The product rarely wants "the k nearest photos": it wants the k nearest of a year, or among the
+ * paths the keyword store returned.  The reference cannot say that to its index, so it inflates
+ * candidate_k, searches unfiltered and throws most of the answer away (core/searcher.py:771-820
+ * _calculate_candidate_k, :887 the search, :573-603 _filter_by_time, :931-936 es_filtered_paths,
+ * :1165-1211 the relaxation rounds that repeat it).  faiss has the missing call --
+ * index.search(q, k, params=SearchParameters(sel=IDSelectorBitmap(n, bitmap))), honoured by
+ * IndexFlat -- and these entries are that call made exact.
+ *
+ * vs_sel_create stands for faiss.IDSelectorBitmap(n, bitmap): id i is allowed iff
+ * (bitmap[i >> 3] >> (i & 7)) & 1 (np.packbits(mask, bitorder="little")).  The selector covers rows
+ * [0, n_sel), n_sel = the index's ntotal at creation: nbytes < ceil(n_sel / 8) is VS_ERR_ARG, bits
+ * at or past n_sel are ignored, rows added later are not selected, and after vs_reset the selector
+ * is stale (searching with it is VS_ERR_ARG).  Creation uploads the bitmap and compacts it once to
+ * an ascending id list on the device; the selector is then reused across searches (the searcher's
+ * relaxation rounds repeat one filter).  It takes the index's shared lock, as searches do. */
+typedef struct vs_sel vs_sel;
+int vs_sel_create(vs_index* index, const uint8_t* bitmap, int64_t nbytes, vs_sel** out);
+void vs_sel_destroy(vs_sel* sel);
+int64_t vs_sel_count(const vs_sel* sel);   /* m: allowed rows */
+/* faiss index.search(q, k, params=SearchParameters(sel=...)) on an IndexFlat: per query the exact
+ * top-k among the allowed rows under the canonical fp64 score -- order, tie rule (lower id) and
+ * D = (float)S as vs_search; with m allowed rows and k > m the slots past m hold -1 / -+FLT_MAX;
+ * k is limited as in vs_search.  Host buffers, staged as vs_search stages them. */
+int vs_search_sel(vs_index* index, const vs_sel* sel, const float* q, int64_t nq, int32_t k, float* D, int64_t* I);
+/* Two tiers answer a filtered search, with identical bits.  SCAN: the exact streaming scan of the
+ * allowed rows alone (nq * m rows gathered).  OVERFETCH: the exact unfiltered search at
+ * k' ~ 1.5 k ntotal / m, filtered on the device; a query whose k' entries hold fewer than k allowed
+ * rows (and k' < ntotal) is re-answered by the scan -- no query is returned from an unproven
+ * prefix.  AUTO (default) picks the scan for 1-2 queries, selective filters and k' past the limit. */
+#define VS_SEL_AUTO 0
+#define VS_SEL_SCAN 1
+#define VS_SEL_OVERFETCH 2
+int vs_set_sel_mode(vs_index* index, int mode);
+/* the last filtered search on this handle, up to `cap` (4) values: {m, tier taken (VS_SEL_SCAN /
+ * VS_SEL_OVERFETCH), k' (0 for the scan), queries re-answered by the scan} */
+int vs_sel_last_stats(vs_index* index, int64_t* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids
@@ -253,6 +291,13 @@ int vs_multi_add(vs_multi* m, const float* x, int64_t n);                       
 int vs_multi_add_from_file(vs_multi* m, const char* path, int64_t byte_offset, int64_t n);
 int vs_multi_write_rows_to_file(vs_multi* m, const char* path, int64_t byte_offset, int64_t i0, int64_t n);
 int vs_multi_search(vs_multi* m, const float* q, int64_t nq, int32_t k, float* D, int64_t* I);
+/* vs_search_sel over the devices (SearchParameters.sel on the one index the reference would hold):
+ * bitmap covers the global ids [0, ntotal) in IDSelectorBitmap's layout.  Rows are dealt in chunks of
+ * 2^16 ids = 8192 bitmap bytes, so each shard's local bitmap is a gather of 8 KiB pieces of the
+ * global one; a per-shard selector is built per call, the shards' filtered searches run as
+ * vs_multi_search runs the unfiltered ones, and the same merge joins them. */
+int vs_multi_search_sel(vs_multi* m, const uint8_t* bitmap, int64_t nbytes, const float* q, int64_t nq,
+                        int32_t k, float* D, int64_t* I);
 int vs_multi_reconstruct_n(vs_multi* m, int64_t i0, int64_t n, float* out);
 int vs_multi_reset(vs_multi* m);
 int vs_multi_set_screen(vs_multi* m, int screen);

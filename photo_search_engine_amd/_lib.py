@@ -95,6 +95,14 @@ _SIGS = {
     "vs_host_staging_bytes": (_c_i64, [_vp]),
     "vs_screen_copy_bytes": (_c_i64, [_vp]),
     "vs_screen_state": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    # id selectors (exact filtered search)
+    "vs_sel_create": (ctypes.c_int, [_vp, _vp, _c_i64, ctypes.POINTER(_vp)]),
+    "vs_sel_destroy": (None, [_vp]),
+    "vs_sel_count": (_c_i64, [_vp]),
+    "vs_search_sel": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_int32, _vp, _vp]),
+    "vs_set_sel_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "vs_sel_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_multi_search_sel": (ctypes.c_int, [_vp, _vp, _c_i64, _vp, _c_i64, ctypes.c_int32, _vp, _vp]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

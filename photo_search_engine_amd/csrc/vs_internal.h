@@ -367,6 +367,35 @@ size_t full_scan_scratch_bytes(int nq, int G, int k);
 void set_lds_attr(const void* fn, int bytes);  // max dynamic LDS of a kernel, set once per device
 hipError_t launch_full_scan(const FullScanArgs& a, hipStream_t st);
 
+// ---- id selectors (vs_selscan.hip) -------------------------------------------------------------
+// device bitmap (64-bit words, faiss IDSelectorBitmap's bit order) -> ascending ids of [0, n_sel) and
+// their count; wgsum: sel_compact_groups(n_sel) words of scratch; ids holds cap entries (the host's
+// count of the same bitmap under the same masking)
+int64_t sel_compact_groups(int64_t n_sel);
+hipError_t launch_sel_compact(const uint64_t* bits, int64_t n_sel, unsigned* wgsum, uint32_t* ids, int64_t cap,
+                              unsigned long long* count, hipStream_t st);
+// the full scan's streaming exact top-k over the m listed rows (ids ascending, each < a.n_valid);
+// a.G workgroups split the list, qy (1..a.nq) query slices deal the block's queries (grid a.G x qy);
+// a.cert / a.all_queries as in launch_full_scan (m < a.k: padded)
+hipError_t launch_sel_scan(const FullScanArgs& a, const uint32_t* ids, int64_t m, int qy, hipStream_t st);
+// the allowed entries of exact unfiltered lists [nq][kp] (best first, -1 padded), the first k each
+struct SelTakeArgs {
+    const uint64_t* bits;   // the selector's bitmap
+    int64_t n_sel;          // ids at or past it are not selected
+    const int64_t* I_in;    // [nq][kp]
+    const float* D_in;      // [nq][kp] (with D)
+    const double* S_in;     // [nq][kp] (with S64)
+    int kp, k, metric;
+    float* D;               // [nq][k] (may be null)
+    int64_t* I;             // [nq][k]
+    double* S64;            // [nq][k] (may be null)
+    const int* cert_in;     // [nq] the unfiltered search's certificates
+    int* found;             // [nq] allowed entries found, capped at k
+    int* cert_out;          // [nq] 1 = the filtered prefix is proven (k found, or the list is exhaustive)
+    int exhaustive;         // the unfiltered lists hold every row of the index
+};
+hipError_t launch_sel_take(const SelTakeArgs& a, int nq, hipStream_t st);
+
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
 // int8 screen copy of stored rows [r0, r0 + n) (maxes[0..1]: running max ||x_hat||, max beta)
@@ -467,6 +496,11 @@ void search_exact_device(vs_index* ix, const float* q_dev, int64_t nq, int k, in
 // the shards that took their rows); the running maxima stay (they only widen certificate margins)
 void truncate_rows(vs_index* ix, int64_t n);
 unsigned* full_scan_counter(vs_index* ix);  // device word behind vs_full_scan_count
+// Exact filtered top-k of device queries (vs_search_sel's tiers; outputs device [nq][k], padded with
+// -1 / the worst score past the allowed rows; k may exceed the rows of a non-empty index).  Synchronises `st` (the overfetch tier reads its
+// per-query counts back).  Takes the index's shared lock.
+void search_sel_device(vs_index* ix, const vs_sel* sel, const float* q_dev, int64_t nq, int k, float* D_dev,
+                       int64_t* I_dev, double* S64_dev, hipStream_t st);
 // S concurrent exact device searches over parts of one batch (own streams and workspaces;
 // unres[i] counts part i's full-scanned queries)
 void search_exact_device_parts(vs_index* ix, const float* q_dev, int64_t nq, int k, int64_t* I_dev,

@@ -531,6 +531,103 @@ int vs_multi_search(vs_multi* m, const float* q, int64_t nq, int32_t k, float* D
     });
 }
 
+// vs_search_sel over the devices.  Shard g holds the global chunks g, g + G, ... of 2^16 ids in
+// order, so its local bitmap is those chunks' 8 KiB pieces of the global bitmap, back to back (the
+// last piece as long as the shard's last chunk).  Each worker builds its shard's selector, runs the
+// shard's filtered search (search_sel_device: fp64 scores + local ids on the device), maps the ids
+// and copies the lists to device 0; the merge is vs_multi_search's.
+int vs_multi_search_sel(vs_multi* m, const uint8_t* bitmap, int64_t nbytes, const float* q, int64_t nq, int32_t k,
+                        float* D, int64_t* I) {
+    return guarded([&] {
+        if (!m) throw VsError(VS_ERR_ARG, "null handle");
+        if (nq < 0) throw VsError(VS_ERR_ARG, "nq must be >= 0");
+        if (k <= 0) throw VsError(VS_ERR_ARG, "k must be > 0");
+        std::shared_lock<std::shared_mutex> lk(m->rw);  // concurrent searches; adds wait
+        if (nbytes < (m->ntotal + 7) / 8 || (m->ntotal > 0 && !bitmap))
+            throw VsError(VS_ERR_ARG, "selector bitmap too short: " + std::to_string((m->ntotal + 7) / 8) +
+                                          " bytes cover ntotal");
+        if (nq == 0) return;
+        if (!q || !D || !I) throw VsError(VS_ERR_ARG, "null host buffer");
+        const float fillD = m->metric == VS_METRIC_IP ? -3.402823466e+38f : 3.402823466e+38f;
+        const int kk = (int)std::min<int64_t>(k, m->ntotal);
+        if (kk == 0) {
+            for (int64_t i = 0; i < nq * k; ++i) {
+                D[i] = fillD;
+                I[i] = -1;
+            }
+            return;
+        }
+        if (kk > KP_MAX * 4 / 5) throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(KP_MAX * 4 / 5) + ")");
+        const int G = m->G;
+        const size_t lb = (size_t)nq * kk;
+        constexpr int64_t kChunkBytes = kChunk / 8;
+        CtxLease L(m);
+        MCtx* c = L.c;
+        {
+            DeviceGuard dg(m->dev[0]);
+            c->gS.ensure(lb * G * sizeof(double));
+            c->gI.ensure(lb * G * sizeof(int64_t));
+            c->oS.ensure(lb * sizeof(double));
+            c->oI.ensure(lb * sizeof(int64_t));
+            c->oD.ensure(lb * sizeof(float));
+        }
+        c->pool->run([&](int g) {
+            DeviceGuard dg(m->dev[g]);
+            hipStream_t s = c->st[g];
+            c->qdev[g].ensure((size_t)nq * m->d * sizeof(float));
+            c->S[g].ensure(lb * sizeof(double));
+            c->I[g].ensure(lb * sizeof(int64_t));
+            double* Sg = c->S[g].as<double>();
+            int64_t* Ig = c->I[g].as<int64_t>();
+            HIP_CHECK(hipMemcpyAsync(c->qdev[g].p, q, (size_t)nq * m->d * sizeof(float), hipMemcpyHostToDevice, s));
+            const int64_t nloc = vs_ntotal(m->ix[g]);
+            std::vector<uint8_t> local((size_t)((nloc + 7) / 8));
+            for (int64_t lc = 0; lc * kChunk < nloc; ++lc) {
+                const int64_t rows = std::min<int64_t>(kChunk, nloc - lc * kChunk);
+                std::memcpy(local.data() + lc * kChunkBytes, bitmap + (lc * G + g) * kChunkBytes, (size_t)((rows + 7) / 8));
+            }
+            vs_sel* sel = nullptr;
+            if (nloc > 0) throw_rc(vs_sel_create(m->ix[g], local.data(), (int64_t)local.size(), &sel));
+            struct SelFree {
+                vs_sel* s;
+                ~SelFree() { vs_sel_destroy(s); }
+            } sel_free{sel};
+            if (sel && vs_sel_count(sel) > 0) {  // (a shard with fewer rows than kk pads its lists)
+                search_sel_device(m->ix[g], sel, c->qdev[g].as<float>(), nq, kk, nullptr, Ig, Sg, s);
+                hipLaunchKernelGGL(k_local_to_global, dim3((unsigned)((lb + 255) / 256)), dim3(256), 0, s, Ig,
+                                   (int64_t)lb, G, g);
+                HIP_CHECK(hipGetLastError());
+            } else {  // an empty shard, or one with no allowed row, contributes only padding
+                std::vector<double> ws(lb, m->metric == VS_METRIC_IP ? -1.7976931348623157e308 : 1.7976931348623157e308);
+                std::vector<int64_t> wi(lb, -1);
+                HIP_CHECK(hipMemcpyAsync(Sg, ws.data(), lb * sizeof(double), hipMemcpyHostToDevice, s));
+                HIP_CHECK(hipMemcpyAsync(Ig, wi.data(), lb * sizeof(int64_t), hipMemcpyHostToDevice, s));
+                HIP_CHECK(hipStreamSynchronize(s));  // (the host vectors go out of scope)
+            }
+            // this shard's lists into slot g of device 0's gather buffers (xGMI peer copy)
+            HIP_CHECK(hipMemcpyPeerAsync(c->gS.as<double>() + lb * g, m->dev[0], Sg, m->dev[g], lb * sizeof(double), s));
+            HIP_CHECK(hipMemcpyPeerAsync(c->gI.as<int64_t>() + lb * g, m->dev[0], Ig, m->dev[g], lb * sizeof(int64_t), s));
+            HIP_CHECK(hipEventRecord(c->ready[g], s));
+            HIP_CHECK(hipStreamSynchronize(s));  // (the per-call selector is freed when the worker returns)
+        });
+        DeviceGuard dg(m->dev[0]);
+        hipStream_t s0 = c->st[0];
+        for (int g = 1; g < G; ++g) HIP_CHECK(hipStreamWaitEvent(s0, c->ready[g], 0));
+        HIP_CHECK(launch_merge_shards(m->metric, c->gS.as<double>(), c->gI.as<int64_t>(), G, nq, kk, c->oS.as<double>(),
+                                      c->oI.as<int64_t>(), c->oD.as<float>(), s0));
+        std::vector<float> Dk(lb);
+        std::vector<int64_t> Ik(lb);
+        HIP_CHECK(hipMemcpyAsync(Dk.data(), c->oD.p, lb * sizeof(float), hipMemcpyDeviceToHost, s0));
+        HIP_CHECK(hipMemcpyAsync(Ik.data(), c->oI.p, lb * sizeof(int64_t), hipMemcpyDeviceToHost, s0));
+        HIP_CHECK(hipStreamSynchronize(s0));  // (s0 waited for every shard's ready event)
+        for (int64_t a = 0; a < nq; ++a)
+            for (int j = 0; j < k; ++j) {
+                D[a * k + j] = j < kk ? Dk[a * kk + j] : fillD;
+                I[a * k + j] = j < kk ? Ik[a * kk + j] : -1;
+            }
+    });
+}
+
 int vs_multi_reconstruct_n(vs_multi* m, int64_t i0, int64_t n, float* out) {
     return guarded([&] {
         if (!m || !out) throw VsError(VS_ERR_ARG, "null argument");

@@ -25,6 +25,79 @@ def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
+def pack_allowed(n: int, allowed) -> np.ndarray:
+    """The bitmap of a selector over rows ``[0, n)`` in faiss ``IDSelectorBitmap``'s layout (id ``i``
+    is allowed iff ``(bitmap[i >> 3] >> (i & 7)) & 1``): ``allowed`` is a boolean mask of length
+    ``n`` or an iterable of row ids (duplicates are fine).  A mask of another length or an id
+    outside ``[0, n)`` raises ``ValueError``."""
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must be >= 0")
+    arr = allowed if isinstance(allowed, np.ndarray) else np.asarray(list(allowed))
+    if arr.dtype == np.bool_:
+        if arr.ndim != 1 or arr.shape[0] != n:
+            raise ValueError(f"a boolean mask must have length {n}, got shape {arr.shape}")
+        mask = arr
+    else:
+        if arr.size == 0:
+            arr = np.zeros((0,), dtype=np.int64)
+        if arr.ndim != 1 or arr.dtype.kind not in "iu":
+            raise ValueError("allowed must be a boolean mask or a 1-D iterable of integer row ids")
+        if arr.size and (int(arr.min()) < 0 or int(arr.max()) >= n):
+            raise ValueError(f"allowed ids must lie in [0, {n})")
+        mask = np.zeros((n,), dtype=bool)
+        mask[arr.astype(np.int64, copy=False)] = True
+    return np.packbits(mask, bitorder="little")
+
+
+SEL_MODES = {"auto": 0, "scan": 1, "overfetch": 2}
+
+
+class Selector:
+    """A set of row ids of one :class:`FlatIndex` (``vs_sel``, include/vs.h): faiss's
+    ``IDSelectorBitmap`` uploaded and compacted once, reused across searches.  It covers the rows
+    present when it was made (rows added later are not selected) and is stale after ``reset()``."""
+
+    def __init__(self, index: "FlatIndex", allowed) -> None:
+        self._h = None
+        self._index = index  # (keeps the index alive while the selector is)
+        self._L = index._L
+        bitmap = np.ascontiguousarray(pack_allowed(index.ntotal, allowed))
+        h = ctypes.c_void_p()
+        check(self._L.vs_sel_create(index._h, _ptr(bitmap), bitmap.shape[0], ctypes.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_bitmap(cls, index: "FlatIndex", bitmap) -> "Selector":
+        """From a packed bitmap (``pack_allowed``'s layout; bits past ``ntotal`` are ignored, a bitmap
+        shorter than ``ceil(ntotal / 8)`` bytes is an argument error)."""
+        self = cls.__new__(cls)
+        self._h = None
+        self._index = index
+        self._L = index._L
+        bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8)
+        h = ctypes.c_void_p()
+        check(self._L.vs_sel_create(index._h, _ptr(bitmap), bitmap.shape[0], ctypes.byref(h)))
+        self._h = h
+        return self
+
+    @property
+    def count(self) -> int:
+        """Allowed rows."""
+        return int(self._L.vs_sel_count(self._h))
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            self._L.vs_sel_destroy(self._h)
+        self._h = None
+
+    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FlatIndex:
     """Exact flat inner-product / squared-L2 index resident in one GPU's HBM."""
 
@@ -60,7 +133,10 @@ class FlatIndex:
             raise ValueError(f"add expects an (n, {self.d}) array, got {x.shape}")
         check(self._L.vs_add(self._h, _ptr(x), x.shape[0]))
 
-    def search(self, q, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, q, k: int, sel=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact top-``k``; with ``sel`` (a :class:`Selector`, a boolean mask or row ids) the exact
+        top-``k`` among the allowed rows -- faiss's ``search(q, k, params=SearchParameters(sel=...))``
+        -- padded with ``-1`` / the worst score when fewer than ``k`` rows are allowed."""
         q = np.ascontiguousarray(q, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError(f"search expects an (nq, {self.d}) array, got {q.shape}")
@@ -70,8 +146,38 @@ class FlatIndex:
             raise _lib.VsError(_lib.VS_ERR_ARG, "k must be > 0")
         D = np.empty((nq, k), dtype=np.float32)
         I = np.empty((nq, k), dtype=np.int64)
-        check(self._L.vs_search(self._h, _ptr(q), nq, k, _ptr(D), _ptr(I)))
+        if sel is None:
+            check(self._L.vs_search(self._h, _ptr(q), nq, k, _ptr(D), _ptr(I)))
+            return D, I
+        own = None if isinstance(sel, Selector) else Selector(self, sel)
+        s = own or sel
+        try:
+            if s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            check(self._L.vs_search_sel(self._h, s._h, _ptr(q), nq, k, _ptr(D), _ptr(I)))
+        finally:
+            if own is not None:
+                own.close()
         return D, I
+
+    def selector(self, allowed) -> Selector:
+        """A reusable :class:`Selector` over the rows present now (mask or ids, ``pack_allowed``)."""
+        return Selector(self, allowed)
+
+    def set_sel_mode(self, mode: str) -> None:
+        """Force the tier of filtered searches (``"scan"``, ``"overfetch"``) or let the library choose
+        (``"auto"``); results are the same bits under every mode (include/vs.h ``vs_set_sel_mode``)."""
+        if mode not in SEL_MODES:
+            raise ValueError(f"unknown selector mode {mode!r}")
+        check(self._L.vs_set_sel_mode(self._h, SEL_MODES[mode]))
+
+    def sel_last_stats(self) -> dict:
+        """The last filtered search: allowed rows, tier taken, the overfetch depth k' and the queries
+        the scan re-answered (include/vs.h ``vs_sel_last_stats``)."""
+        buf = (ctypes.c_int64 * 4)()
+        check(self._L.vs_sel_last_stats(self._h, buf, 4))
+        return {"m": int(buf[0]), "tier": {1: "scan", 2: "overfetch"}.get(int(buf[1]), "none"),
+                "kprime": int(buf[2]), "rescanned": int(buf[3])}
 
     def reconstruct(self, i: int) -> np.ndarray:
         out = np.empty((self.d,), dtype=np.float32)
@@ -258,6 +364,22 @@ class FlatIndex:
             pass
 
 
+class MaskSelector:
+    """:meth:`MultiDeviceFlatIndex.selector`: the packed bitmap of a filter over the rows present
+    when it was made, kept on the host (the per-shard selectors are built per search)."""
+
+    def __init__(self, n: int, allowed) -> None:
+        self.n = int(n)
+        self.bitmap = np.ascontiguousarray(pack_allowed(self.n, allowed))
+
+    @property
+    def count(self) -> int:
+        return int(np.unpackbits(self.bitmap, bitorder="little")[: self.n].sum())
+
+    def close(self) -> None:
+        pass
+
+
 def merge_shards_device(metric_type: int, S_ptr: int, I_ptr: int, G: int, nq: int, k: int, S_out: int, I_out: int,
                         D_out: Optional[int] = None, stream: Optional[int] = None, in_stride: int = 1) -> None:
     """Merge G per-shard sorted (S64, id) lists [G][nq][k] on the device (after an all-gather);
@@ -338,7 +460,10 @@ class MultiDeviceFlatIndex:
         self._drop_prune_copy()
         check(self._L.vs_multi_add(self._h, _ptr(x), x.shape[0]))
 
-    def search(self, q, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, q, k: int, sel=None) -> Tuple[np.ndarray, np.ndarray]:
+        """Exact top-``k`` over all devices; ``sel`` (a boolean mask over the global ids, ids, or a
+        :class:`MaskSelector` from :meth:`selector`): the exact top-``k`` among the allowed rows
+        (``vs_multi_search_sel``)."""
         q = np.ascontiguousarray(q, dtype=np.float32)
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError(f"search expects an (nq, {self.d}) array, got {q.shape}")
@@ -347,8 +472,22 @@ class MultiDeviceFlatIndex:
             raise _lib.VsError(_lib.VS_ERR_ARG, "k must be > 0")
         D = np.empty((q.shape[0], k), dtype=np.float32)
         I = np.empty((q.shape[0], k), dtype=np.int64)
-        check(self._L.vs_multi_search(self._h, _ptr(q), q.shape[0], k, _ptr(D), _ptr(I)))
+        if sel is None:
+            check(self._L.vs_multi_search(self._h, _ptr(q), q.shape[0], k, _ptr(D), _ptr(I)))
+        else:  # (per-shard selectors are built per call)
+            n = self.ntotal
+            if isinstance(sel, MaskSelector):  # rows added after it was made are not selected
+                bitmap = np.zeros(((n + 7) // 8,), dtype=np.uint8)
+                bitmap[: sel.bitmap.shape[0]] = sel.bitmap[: bitmap.shape[0]]
+            else:
+                bitmap = np.ascontiguousarray(pack_allowed(n, sel))
+            check(self._L.vs_multi_search_sel(self._h, _ptr(bitmap), bitmap.shape[0], _ptr(q), q.shape[0], k,
+                                              _ptr(D), _ptr(I)))
         return D, I
+
+    def selector(self, allowed) -> MaskSelector:
+        """A reusable filter over the rows present now (mask or ids, ``pack_allowed``)."""
+        return MaskSelector(self.ntotal, allowed)
 
     def reconstruct_n(self, i0: int, n: int) -> np.ndarray:
         out = np.empty((int(n), self.d), dtype=np.float32)

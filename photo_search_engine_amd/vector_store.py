@@ -282,15 +282,30 @@ class VectorStore:
             self._path_to_index[photo_path] = len(self.metadata) - 1
 
     # 内部接口：仅允许searcher模块调用，禁止前端直接访问向量数据库
-    def search(self, query_embedding: List[float], top_k: int) -> List[Dict]:
-        """相似度检索 (utils/vector_store.py:172-198)."""
+    def search(self, query_embedding: List[float], top_k: int, allowed=None) -> List[Dict]:
+        """相似度检索 (utils/vector_store.py:172-198).
+
+        ``allowed`` (an addition at the boundary; ``None`` = the reference's call, untouched): the
+        exact ``top_k`` among the allowed items only -- a :class:`~.index.Selector` from
+        :meth:`selector`, a boolean mask over the items, item ids, or a predicate applied to each
+        item's metadata.  The reference body (guards, ``k = min(top_k, ntotal)``, normalisation,
+        ``-1`` filtering, result dicts) around faiss's ``search(..., params=SearchParameters(sel=
+        IDSelectorBitmap(...)))``: a filter matching fewer than ``top_k`` items returns them all,
+        and one matching enough never returns fewer than ``top_k`` (what over-fetching and
+        post-filtering cannot promise, core/searcher.py:771-820, :573-603).  HNSW stores with
+        ``VECTOR_HNSW_SEARCH=graph`` answer filtered calls exactly through the flat path, as
+        multi-GPU indexes answer every call."""
         if self.index is None or self.index.ntotal == 0:
             return []
         if len(query_embedding) != self.dimension:
             raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
 
         k = min(top_k, self.index.ntotal)
-        distances, indices = self._search_rows(self._normalize_query(query_embedding), k)
+        if allowed is None:
+            distances, indices = self._search_rows(self._normalize_query(query_embedding), k)
+        else:
+            distances, indices = self.index.search(self._normalize_query(query_embedding), k,
+                                                   sel=self._allowed_rows(allowed))
 
         results: List[Dict] = []
         for distance, index in zip(distances[0].tolist(), indices[0].tolist()):
@@ -298,6 +313,21 @@ class VectorStore:
                 continue
             results.append({"metadata": self.metadata[index], "distance": float(distance)})
         return results
+
+    def _allowed_rows(self, allowed):
+        """A predicate over the metadata as a boolean mask over the items; selectors, masks and ids pass."""
+        if callable(allowed):
+            n = int(self.index.ntotal)
+            return np.fromiter((bool(allowed(m)) for m in self.metadata[:n]), dtype=bool, count=n)
+        return allowed
+
+    def selector(self, allowed):
+        """A reusable selector for :meth:`search`'s ``allowed`` (the searcher's relaxation rounds repeat
+        one filter): a boolean mask, item ids, or a predicate applied to each ``self.metadata[i]``.
+        It covers the items present now and is stale after :meth:`clear`."""
+        if self.index is None:
+            raise RuntimeError("the store has no index yet")
+        return self.index.selector(self._allowed_rows(allowed))
 
     def get_embedding_by_photo_path(self, photo_path: str) -> Optional[List[float]]:
         index = self._path_to_index.get(photo_path)
