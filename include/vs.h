@@ -77,7 +77,10 @@ int vs_synthesize(int device, uint64_t seed, int64_t global_row0, int64_t n, int
 
 /* ---- search (index.search, utils/vector_store.py:191).  Exact for every query: a failed
  * certificate re-screens the query 4x deeper, and past the deepest screen (KP_MAX) the exact full
- * scan answers it (faiss's k lowest ids among any number of tied rows). */
+ * scan answers it (faiss's k lowest ids among any number of tied rows).  Value domain: exactness
+ * holds, and is tested, for finite stored values with row and query norms zero or in [2^-40, 2^40];
+ * beyond it (fp32 ||x||^2 under- or overflows, f16 rows saturate from 65520, scores leave fp32's
+ * normal range) results are unspecified, and non-finite inputs are not validated. */
 int vs_search(vs_index* index, const float* q, int64_t nq, int32_t k, float* D, int64_t* I);
 /* All pointers device-resident; enqueued on `stream` (NULL = the legacy default stream, which is
  * torch's default stream: device calls are always ordered with the caller's stream), no host

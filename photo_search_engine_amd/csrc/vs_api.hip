@@ -436,10 +436,15 @@ void health_note(vs_index* ix, Ctx* c, hipStream_t st, int kind, int nq) {
 // N(0, 1/d) and the k-th best sits z = sqrt(2 ln(N / k)) deviations out, where the density grows by
 // e^(z beta sqrt(d)) per beta: keep k times twice that (+64); deeper than kI8GemvMaxDepth, the
 // native GEMV serves the query.  Data that defeat the estimate fail the certificate, not exactness.
+// beta enters relative to max ||x||, so the depth does not depend on the rows' scale (as an absolute
+// norm it sent every index of rows scaled by 2^12 to the native GEMV and cut one scaled by 2^-40
+// to the minimum depth).
 constexpr int kI8GemvMaxDepth = 512;
 int i8_gemv_depth(const vs_index* ix, int k) {
     const double z = std::sqrt(2.0 * std::log(std::max(2.0, (double)ix->ntotal / k)));
-    const double g = std::exp(std::min(20.0, z * (double)ix->i8_bmax * std::sqrt((double)ix->d)));
+    const double xm = std::sqrt((double)ix->maxsq);
+    const double beta = xm > 0.0 ? (double)ix->i8_bmax / xm : 0.0;
+    const double g = std::exp(std::min(20.0, z * beta * std::sqrt((double)ix->d)));
     return (int)std::min<double>(KP_MAX, round_up((int64_t)std::ceil(2.0 * k * g + 64.0), 16));
 }
 // Union of survivors the int8 seed aims at (rows above the seeded threshold).  It must cover the

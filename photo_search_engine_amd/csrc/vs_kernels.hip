@@ -1432,8 +1432,16 @@ __device__ __forceinline__ void refine(const RefineArgs& a, int KP2) {
             }
             double tk = sc[a.k - 1];
             if (a.metric == METRIC_L2) {
-                eps = 2.0 * eps + ((double)a.gamma + 4.0 * 5.9604644775390625e-08) * (xm * xm + 2.0 * xm * qh) * 1.01 +
-                      1e-12 * (qq_s + xm * xm);
+                // A row of norm n lies at distance >= (n - ||q||)^2, so one with n above ||q|| + sqrt(D_k)
+                // is farther than the k-th best whatever its key (1e-4 covers the fp64 roundings of the
+                // canonical distance, ~1e-12 relative, and keeps exact ties out).  The margin therefore
+                // only has to bound the key error of rows up to that norm: with the global max ||x|| a
+                // few large rows among small ones made every query uncertifiable (and, with more than
+                // KP_MAX probed rows, an IVF search fail).  Unit rows and queries: xe = xm.
+                const double xe = fmin(xm, (sqrt(qq_s) + sqrt(fmax(tk, 0.0))) * (1.0 + 1e-4));
+                if (!a.i8max) eps = ((double)a.gamma * qh + dq) * xe * 1.01 + 1e-30;
+                eps = 2.0 * eps + ((double)a.gamma + 4.0 * 5.9604644775390625e-08) * (xe * xe + 2.0 * xe * qh) * 1.01 +
+                      1e-12 * (qq_s + xe * xe);
                 tk = qq_s - tk;
             }
             cert = tk > smin + eps ? 1 : 0;
