@@ -277,6 +277,48 @@ int vs_set_sel_mode(vs_index* index, int mode);
  * VS_SEL_OVERFETCH), k' (0 for the scan), queries re-answered by the scan} */
 int vs_sel_last_stats(vs_index* index, int64_t* out, int cap);
 
+/* ==== range search: every row within a score radius ==========================================
+ * faiss IndexFlat::range_search(x, radius) -> (lims, D, I).  The reference cuts a guessed top-k at
+ * score floors (core/searcher.py:822-843, over the candidate list of :771-820); this call returns
+ * exactly the rows that pass the floor, however many there are.
+ *
+ * For query q with radius r_q (fp32, one per query) and a row of canonical fp64 score S (as
+ * vs_search defines it), D = (float)S: the row is returned iff D > r_q (inner product) or D < r_q
+ * (L2, squared distance) -- strict, as faiss, and on the fp32 value the caller sees, so a row is
+ * returned exactly when vs_search would report a D that satisfies it.  Each query's rows come best
+ * first under vs_search's total order (S, then the lower id): a range result equals the first
+ * `count` entries of vs_search(k >= count).  radius -inf (IP) / +inf (L2) returns every row; a NaN
+ * radius is VS_ERR_ARG; nq = 0 gives lims = {0}; an empty index gives all-zero lims.
+ *
+ * The result is an owned object (faiss's RangeSearchResult); its size depends on the data, so the
+ * call synchronises.  max_total > 0 caps lims[nq]: beyond it the call is VS_ERR_ARG, the message
+ * names the count needed and *out is untouched; <= 0 = no cap.  sel may be NULL; with a selector the
+ * rules of vs_search_sel hold (a stale selector is VS_ERR_ARG, rows added later are not selected). */
+typedef struct vs_range_result vs_range_result;
+int vs_range_search(vs_index* index, const vs_sel* sel, const float* q, int64_t nq, const float* radius,
+                    int64_t max_total, vs_range_result** out);
+const int64_t* vs_range_lims(const vs_range_result* r);   /* nq + 1 */
+const float* vs_range_D(const vs_range_result* r);        /* lims[nq] */
+const int64_t* vs_range_I(const vs_range_result* r);      /* lims[nq] */
+int64_t vs_range_nq(const vs_range_result* r);
+void vs_range_free(vs_range_result* r);
+/* Two tiers answer a range search, with identical bits.  SCAN (every dtype and metric, any nq, and
+ * the only tier with a selector): the exact streaming scan, every row scored canonically.  SCREEN
+ * (bf16 / f16 rows, blocks of 9..256 queries, no selector): the native MFMA screen started at the
+ * key of r_q lowered by the screen's proven margin, so its survivors are a superset of the answer;
+ * they are scored exactly and tested.  A query whose survivor list a workgroup had to cut is
+ * re-answered by the scan -- no query is returned from a list that may be incomplete.  AUTO
+ * (default): SCREEN where it applies, otherwise SCAN.  The int8 screen setting (vs_set_screen) does
+ * not apply to range searches: they always screen the stored rows. */
+#define VS_RANGE_AUTO 0
+#define VS_RANGE_SCAN 1
+#define VS_RANGE_SCREEN 2
+int vs_set_range_mode(vs_index* index, int mode);
+/* the last range search on this handle, up to `cap` (4) values: {total results, tier taken for the
+ * batch (VS_RANGE_SCREEN if any block was screened), queries re-answered by the scan after a screen
+ * overflow, queries whose segment (longer than 4096 rows) was sorted on the host} */
+int vs_range_last_stats(vs_index* index, int64_t* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids
@@ -301,6 +343,11 @@ int vs_multi_search(vs_multi* m, const float* q, int64_t nq, int32_t k, float* D
  * vs_multi_search runs the unfiltered ones, and the same merge joins them. */
 int vs_multi_search_sel(vs_multi* m, const uint8_t* bitmap, int64_t nbytes, const float* q, int64_t nq,
                         int32_t k, float* D, int64_t* I);
+/* vs_range_search over the devices: bitmap (NULL = no filter) as in vs_multi_search_sel; every
+ * shard's range search runs on its own worker and stream, local ids become global ids and each
+ * query's shard segments are merged on the host under the same order.  Equals one index over all rows. */
+int vs_multi_range_search(vs_multi* m, const uint8_t* bitmap, int64_t nbytes, const float* q, int64_t nq,
+                          const float* radius, int64_t max_total, vs_range_result** out);
 int vs_multi_reconstruct_n(vs_multi* m, int64_t i0, int64_t n, float* out);
 int vs_multi_reset(vs_multi* m);
 int vs_multi_set_screen(vs_multi* m, int screen);

@@ -103,6 +103,14 @@ _SIGS = {
     "vs_set_sel_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "vs_sel_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_multi_search_sel": (ctypes.c_int, [_vp, _vp, _c_i64, _vp, _c_i64, ctypes.c_int32, _vp, _vp]),
+    # range search
+    "vs_range_search": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, ctypes.POINTER(_vp)]),
+    "vs_range_lims": (_vp, [_vp]),
+    "vs_range_nq": (_c_i64, [_vp]),
+    "vs_range_free": (None, [_vp]),
+    "vs_set_range_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "vs_range_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_multi_range_search": (ctypes.c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.POINTER(_vp)]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),
@@ -151,6 +159,13 @@ _SIGS = {
     "vs_hnsw_prune": (ctypes.c_int, [_vp, _c_i64, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp]),
 }
 
+# entry points whose names carry capitals (faiss's D / I): bound like the table above, kept apart
+# because header_functions() lists lower-case names only
+_SIGS_DI = {
+    "vs_range_D": (_vp, [_vp]),
+    "vs_range_I": (_vp, [_vp]),
+}
+
 
 def header_functions(path: str = HEADER_PATH):
     """Names of every function include/vs.h declares (used by the symbol-export test)."""
@@ -181,7 +196,7 @@ def load(path: Optional[str] = None) -> ctypes.CDLL:
                 f"libvs.so not found at {path}: the HIP library is the only implementation of this path; "
                 "build it with `python -m photo_search_engine_amd.build` (hipcc, gfx950)")
         L = ctypes.CDLL(path)
-        for name, (res, args) in _SIGS.items():
+        for name, (res, args) in list(_SIGS.items()) + list(_SIGS_DI.items()):
             if path != LIB_PATH and not hasattr(L, name):
                 continue  # (an A/B build from before an entry point was added)
             fn = getattr(L, name)

@@ -396,6 +396,59 @@ struct SelTakeArgs {
 };
 hipError_t launch_sel_take(const SelTakeArgs& a, int nq, hipStream_t st);
 
+// ---- range search (vs_range.hip) ---------------------------------------------------------------
+// Every row whose fp32 score D = (float)S passes a per-query radius (D > r inner product, D < r L2),
+// collected as (S, id) pairs in per-query regions of a pair buffer: query q appends at
+// psc / pid[off[q] + pos], pos taken from cnt[q] by an atomic add; a pair is stored only while
+// pos < cap[q], cnt[q] keeps counting past it (the host reruns the query with a region of that size).
+constexpr int RS_SORT_MAX = 4096;  // longest segment k_range_emit sorts in LDS (sort_valid_best_first)
+struct RangeArgs {
+    const uint8_t* corpus;  // tiled shard
+    int d, dpad, dt, metric;
+    int64_t n_valid;
+    const float* q;         // [nq][d] fp32 queries of the block
+    int nq;
+    const float* radius;    // [nq]
+    const int* go;          // [nq]: queries with go[q] == 0 are left alone, or null = every query
+    double* psc;            // pair buffer: canonical fp64 scores (IP score / squared L2 distance) ...
+    uint32_t* pid;          // ... and local row ids
+    const int64_t* off;     // [nq] first slot of the query's region
+    const int64_t* cap;     // [nq] slots of the region (0 = count only)
+    unsigned long long* cnt;  // [nq] passing rows found (zeroed by the host before the launch)
+};
+// SCAN tier: G workgroups split the n_valid rows, or the m listed rows ids[0, m) (ascending, each <
+// n_valid) when ids is given; qy (1..nq) query slices deal the block's queries (grid G x qy)
+hipError_t launch_range_scan(const RangeArgs& a, int G, int qy, const uint32_t* ids, int64_t m, hipStream_t st);
+// SCREEN tier, threshold: thr0[q] = a key below every key the native screen can give a row that
+// passes radius[q] (0 = keep every row); qinfo / xmax / gamma as RefineArgs
+hipError_t launch_range_thr(int metric, const float* radius, const float* qinfo, const float* q, int d, int nq,
+                            float xmax, float gamma, u64* thr0, hipStream_t st);
+// SCREEN tier, refine: the survivors glist[q][0, min(gcnt[q], lcap)) scored exactly and tested; ny
+// workgroups per query share a list
+hipError_t launch_range_refine(const RangeArgs& a, const u64* glist, const int* gcnt, int lcap, int ny,
+                               hipStream_t st);
+// one query's segment of the pair buffers -> its place in the block's outputs
+struct RangeSeg {
+    int64_t src;  // first slot in pair buffer `buf`
+    int64_t n;    // pairs
+    int64_t dst;  // first output slot
+    int buf;      // 0 / 1
+    int pad;
+};
+struct RangeEmitArgs {
+    const double* psc[2];
+    const uint32_t* pid[2];
+    const RangeSeg* seg;  // [nq]
+    int metric;
+    int64_t id_offset;
+    float* D;             // outputs: D = (float)S, I = id + id_offset, S
+    int64_t* I;
+    double* S;
+};
+// one workgroup per query: segments of at most RS_SORT_MAX pairs are written best first (S, then
+// the lower id), longer ones as they are (the host sorts them)
+hipError_t launch_range_emit(const RangeEmitArgs& a, int nq, hipStream_t st);
+
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
 // int8 screen copy of stored rows [r0, r0 + n) (maxes[0..1]: running max ||x_hat||, max beta)
@@ -459,8 +512,16 @@ hipError_t launch_pack_rows_map(int dt, const float* src, int64_t n, int d, int 
 
 #include <functional>
 #include <shared_mutex>
+#include <vector>
 
 struct vs_index;
+// the owned result of a range search (include/vs.h): query q's rows are [lims[q], lims[q + 1])
+struct vs_range_result {
+    std::vector<int64_t> lims;
+    std::vector<float> D;
+    std::vector<int64_t> I;
+    std::vector<double> S;  // canonical fp64 scores of the same rows (internal)
+};
 namespace vs {
 // the stored rows of a flat index as the kernels see them; read it (and launch on it) while holding
 // flat_lock(ix) shared, the lock adds and resets take exclusively
@@ -501,6 +562,10 @@ unsigned* full_scan_counter(vs_index* ix);  // device word behind vs_full_scan_c
 // per-query counts back).  Takes the index's shared lock.
 void search_sel_device(vs_index* ix, const vs_sel* sel, const float* q_dev, int64_t nq, int k, float* D_dev,
                        int64_t* I_dev, double* S64_dev, hipStream_t st);
+// Exact range search of host queries (vs_range_search's body: lock, lease, tiers); the result's ids
+// are local row ids, its S the canonical fp64 scores (kept for the multi-device merge).
+void range_search_host(vs_index* ix, const vs_sel* sel, const float* q, int64_t nq, const float* radius,
+                       int64_t max_total, vs_range_result* out);
 // S concurrent exact device searches over parts of one batch (own streams and workspaces;
 // unres[i] counts part i's full-scanned queries)
 void search_exact_device_parts(vs_index* ix, const float* q_dev, int64_t nq, int k, int64_t* I_dev,

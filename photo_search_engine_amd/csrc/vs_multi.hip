@@ -24,6 +24,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <thread>
@@ -625,6 +626,88 @@ int vs_multi_search_sel(vs_multi* m, const uint8_t* bitmap, int64_t nbytes, cons
                 D[a * k + j] = j < kk ? Dk[a * kk + j] : fillD;
                 I[a * k + j] = j < kk ? Ik[a * kk + j] : -1;
             }
+    });
+}
+
+int vs_multi_range_search(vs_multi* m, const uint8_t* bitmap, int64_t nbytes, const float* q, int64_t nq,
+                          const float* radius, int64_t max_total, vs_range_result** out) {
+    return guarded([&] {
+        if (!m) throw VsError(VS_ERR_ARG, "null handle");
+        if (!out) throw VsError(VS_ERR_ARG, "out is null");
+        if (nq < 0) throw VsError(VS_ERR_ARG, "nq must be >= 0");
+        std::shared_lock<std::shared_mutex> lk(m->rw);  // concurrent searches; adds wait
+        if (bitmap && nbytes < (m->ntotal + 7) / 8)
+            throw VsError(VS_ERR_ARG, "selector bitmap too short: " + std::to_string((m->ntotal + 7) / 8) +
+                                          " bytes cover ntotal");
+        std::unique_ptr<vs_range_result> res(new vs_range_result());
+        res->lims.assign((size_t)nq + 1, 0);
+        if (nq > 0 && (!q || !radius)) throw VsError(VS_ERR_ARG, "null host buffer");
+        for (int64_t i = 0; i < nq; ++i)
+            if (radius[i] != radius[i]) throw VsError(VS_ERR_ARG, "radius is NaN (query " + std::to_string(i) + ")");
+        if (nq == 0 || m->ntotal == 0) {
+            *out = res.release();
+            return;
+        }
+        const int G = m->G;
+        constexpr int64_t kChunkBytes = kChunk / 8;
+        std::vector<vs_range_result> part((size_t)G);
+        CtxLease L(m);
+        // every shard's range search on its own worker (and the stream of the context it leases),
+        // local ids mapped to global ids as k_local_to_global maps them
+        L.c->pool->run([&](int g) {
+            const int64_t nloc = vs_ntotal(m->ix[g]);
+            part[g].lims.assign((size_t)nq + 1, 0);
+            if (nloc == 0) return;
+            vs_sel* sel = nullptr;
+            if (bitmap) {
+                std::vector<uint8_t> local((size_t)((nloc + 7) / 8));
+                for (int64_t lc = 0; lc * kChunk < nloc; ++lc) {
+                    const int64_t rows = std::min<int64_t>(kChunk, nloc - lc * kChunk);
+                    std::memcpy(local.data() + lc * kChunkBytes, bitmap + (lc * G + g) * kChunkBytes,
+                                (size_t)((rows + 7) / 8));
+                }
+                throw_rc(vs_sel_create(m->ix[g], local.data(), (int64_t)local.size(), &sel));
+            }
+            struct SelFree {
+                vs_sel* s;
+                ~SelFree() { vs_sel_destroy(s); }
+            } sel_free{sel};
+            range_search_host(m->ix[g], sel, q, nq, radius, 0, &part[g]);
+            for (int64_t& id : part[g].I)
+                id = ((((id >> kChunkBits) * G) + g) << kChunkBits) | (id & (kChunk - 1));
+        });
+        // each query's shard segments (each best first) merged under the same order: S, then the
+        // lower global id
+        int64_t total = 0;
+        for (int64_t a = 0; a < nq; ++a) {
+            for (int g = 0; g < G; ++g) total += part[g].lims[a + 1] - part[g].lims[a];
+            res->lims[a + 1] = total;
+        }
+        if (max_total > 0 && total > max_total)
+            throw VsError(VS_ERR_ARG, "range search found " + std::to_string(total) + " results, max_total is " +
+                                          std::to_string(max_total));
+        res->D.resize((size_t)total);
+        res->I.resize((size_t)total);
+        const bool ip = m->metric == VS_METRIC_IP;
+        std::vector<std::pair<double, int64_t>> seg;
+        for (int64_t a = 0; a < nq; ++a) {
+            seg.clear();
+            for (int g = 0; g < G; ++g) {
+                const size_t mid = seg.size();
+                for (int64_t j = part[g].lims[a]; j < part[g].lims[a + 1]; ++j) seg.emplace_back(part[g].S[j], part[g].I[j]);
+                std::inplace_merge(seg.begin(), seg.begin() + mid, seg.end(),
+                                   [ip](const std::pair<double, int64_t>& x, const std::pair<double, int64_t>& y) {
+                                       if (x.first != y.first) return ip ? x.first > y.first : x.first < y.first;
+                                       return x.second < y.second;
+                                   });
+            }
+            const int64_t o = res->lims[a];
+            for (size_t j = 0; j < seg.size(); ++j) {
+                res->D[o + j] = (float)seg[j].first;
+                res->I[o + j] = seg[j].second;
+            }
+        }
+        *out = res.release();
     });
 }
 

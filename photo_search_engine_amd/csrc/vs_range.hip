@@ -1,0 +1,303 @@
+// vs_range.hip -- exact range search: every row within a score radius (include/vs.h "range search").
+//
+// faiss answers "which rows score at least this well" with IndexFlat::range_search; the reference
+// product cuts a guessed top-k at score floors instead (core/searcher.py:822-843 of the reference).
+// A row belongs to query q's answer iff D = (float)S passes the radius (D > r_q inner product,
+// D < r_q squared L2), S the canonical fp64 score of exact_score_rows (vs_device.h).  Kernels:
+//   * k_range_scan (SCAN tier): streams like fs_scan_body -- workgroup b takes positions
+//     [n b / G, n (b + 1) / G) of the row sequence, or of a selector's ascending id list -- scores
+//     every row with exact_score_rows and tests it.  The output size is unknown, so this file takes
+//     the ONE-PASS design: passing (S, id) pairs are appended to the query's region of a bounded pair
+//     buffer through a wave-aggregated atomic (the wave's lane 0 holds its rows' scores and adds
+//     their count once); a pair is stored only while its slot is inside the region, the counter
+//     keeps counting past the end, and the host reruns an overflowed query with a region of the
+//     counted size.  No row is scored twice unless its query overflowed.
+//   * k_range_thr + k_range_refine (SCREEN tier): the native MFMA screen (launch_screen_mfma, as
+//     vs_search launches it) starts at thr0[q], a key below every key a passing row can get (the
+//     proof is at k_range_thr); k_range_refine scores each query's survivors exactly, several rows
+//     per wave in flight as the refine does, applies the exact predicate and appends the passing
+//     pairs as the scan does.
+//   * k_range_emit: one workgroup per query sorts its segment best first in LDS
+//     (sort_valid_best_first, up to RS_SORT_MAX pairs) and writes D = (float)S, I and S at the
+//     query's offset; longer segments are copied as they are and sorted on the host.
+// Every store is bounded by a capacity the host allocated: a pair slot by cap[q], an output slot by
+// the segment lengths the host read back.  Plain vector stores and returning atomics only.
+#include "vs_scan.h"
+
+namespace vs {
+
+constexpr size_t RS_QLDS_MAX = 48 * 1024;  // the fp64 query is staged in LDS up to this size
+
+__device__ __forceinline__ bool rs_pass(double S, float r, int metric) {
+    const float D = (float)S;
+    return metric == METRIC_IP ? D > r : D < r;
+}
+
+// lane 0 of a wave: append the passing rows among its R scored rows to query q's region
+template <int METRIC, int R>
+__device__ __forceinline__ void rs_append(const RangeArgs& a, int q, float rq, int64_t off, int64_t cap,
+                                          const int64_t (&rr)[R], const double (&s)[R]) {
+    unsigned pass = 0u;
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+        if (rr[i] >= 0 && rs_pass(s[i], rq, METRIC)) pass |= 1u << i;
+    if (!pass) return;
+    unsigned long long pos = atomicAdd(a.cnt + q, (unsigned long long)__popc(pass));
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+        if ((pass >> i) & 1u) {
+            if ((int64_t)pos < cap) {
+                a.psc[off + (int64_t)pos] = s[i];
+                a.pid[off + (int64_t)pos] = (uint32_t)rr[i];
+            }
+            ++pos;
+        }
+}
+
+template <bool QLDS>
+__device__ __forceinline__ void rs_stage_query(double* qs, const float* qv, int d, int ng) {
+    if constexpr (QLDS)
+        for (int i = threadIdx.x; i < d; i += FS_THREADS) qs[(i & 7) * ng + (i >> 3)] = (double)qv[i];
+}
+
+// ---- SCAN tier ------------------------------------------------------------------------------------
+template <int DT, int METRIC, bool QLDS, bool SEL>
+__global__ void __launch_bounds__(FS_THREADS) k_range_scan(RangeArgs a, const uint32_t* __restrict__ ids, int64_t m) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    double* qs = (double*)smem;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x, G = gridDim.x;
+    const int ng = (a.d + 7) >> 3;
+    constexpr int RR = fs_rows<DT>();
+    const int64_t nseq = SEL ? m : a.n_valid;
+    const int64_t r0 = nseq * b / G, r1 = nseq * (b + 1) / G;
+    for (int q = blockIdx.y; q < a.nq; q += gridDim.y) {
+        if (a.go && a.go[q] == 0) continue;  // (block-uniform)
+        __syncthreads();                     // (the previous query's readers of qs are done)
+        const float* qv = a.q + (int64_t)q * a.d;
+        rs_stage_query<QLDS>(qs, qv, a.d, ng);
+        __syncthreads();
+        const float rq = a.radius[q];
+        const int64_t off = a.off[q], cap = a.cap[q];
+        for (int64_t base = r0; base < r1; base += FS_NW * RR) {
+            int64_t rr[RR];
+#pragma unroll
+            for (int i = 0; i < RR; ++i) {
+                const int64_t r = base + wid + (int64_t)i * FS_NW;
+                if constexpr (SEL) rr[i] = r < r1 ? (int64_t)ids[r] : -1;
+                else rr[i] = r < r1 ? r : -1;
+            }
+            if (rr[0] < 0) continue;  // (wave-uniform)
+            double s[RR];
+            exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
+            if (lane == 0) rs_append<METRIC, RR>(a, q, rq, off, cap, rr, s);
+        }
+    }
+}
+
+template <int DT, int METRIC, bool QLDS>
+static void launch_range_scan_one(const RangeArgs& a, int G, int qy, size_t lds, const uint32_t* ids, int64_t m,
+                                  hipStream_t st) {
+    if (ids)
+        hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true>), dim3(G, qy), dim3(FS_THREADS), lds, st, a, ids, m);
+    else
+        hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false>), dim3(G, qy), dim3(FS_THREADS), lds, st, a, ids, m);
+}
+
+template <int DT>
+static void launch_range_scan_dt(const RangeArgs& a, int G, int qy, const uint32_t* ids, int64_t m, hipStream_t st) {
+    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
+    const bool qlds = qbytes <= RS_QLDS_MAX;
+    const size_t lds = qlds ? qbytes : 0;
+    if (a.metric == METRIC_IP) {
+        if (qlds) launch_range_scan_one<DT, METRIC_IP, true>(a, G, qy, lds, ids, m, st);
+        else launch_range_scan_one<DT, METRIC_IP, false>(a, G, qy, lds, ids, m, st);
+    } else {
+        if (qlds) launch_range_scan_one<DT, METRIC_L2, true>(a, G, qy, lds, ids, m, st);
+        else launch_range_scan_one<DT, METRIC_L2, false>(a, G, qy, lds, ids, m, st);
+    }
+}
+
+static bool range_args_ok(const RangeArgs& a) {
+    return a.corpus && a.q && a.radius && a.off && a.cap && a.cnt && a.psc && a.pid && a.nq > 0 && a.d > 0 &&
+           a.n_valid > 0 && (a.metric == METRIC_IP || a.metric == METRIC_L2);
+}
+
+hipError_t launch_range_scan(const RangeArgs& a, int G, int qy, const uint32_t* ids, int64_t m, hipStream_t st) {
+    if (!range_args_ok(a) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) || (!ids && m != 0))
+        return hipErrorInvalidValue;
+    if (a.dt == DT_F32) launch_range_scan_dt<DT_F32>(a, G, qy, ids, m, st);
+    else if (a.dt == DT_BF16) launch_range_scan_dt<DT_BF16>(a, G, qy, ids, m, st);
+    else if (a.dt == DT_F16) launch_range_scan_dt<DT_F16>(a, G, qy, ids, m, st);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ---- SCREEN tier: the starting threshold ------------------------------------------------------------
+// The screen's key of a row is its fp32 MFMA score over the dtype-rounded query q^ (inner product:
+// <x, q^>; L2: 2 <x, q^> - ||x||^2, the transformed score qq - dist up to the constant qq = ||q||^2).
+// The refine's certificate (refine(), vs_kernels.hip) rests on the bound  t <= key + eps  for every
+// row, t the exact transformed score, with
+//   IP:  eps = (gamma ||q^|| + ||q^ - q||) xmax 1.01
+//   L2:  eps = 2 (gamma ||q^|| + ||q^ - q||) xe 1.01 + (gamma + 4u)(xe^2 + 2 xe ||q^||) 1.01 + 1e-12 (qq + xe^2),
+//        xe an upper bound of the norm of every row that matters: a row at distance < r has
+//        ||x|| <= ||q|| + sqrt(r), so xe = min(xmax, (||q|| + sqrt(r)) (1 + 1e-4)).
+// Survivors contain the answer: a row in the answer has D past r, hence S past r (r is an fp32 value
+// and the rounding is monotonic), hence t > T (T = r for IP, qq - r for L2), hence key >= t - eps >
+// T - eps >= key_score(thr0): the screen keeps it (keys > thr0), unless a workgroup compacts -- which
+// it reports in drop[q].
+__global__ void __launch_bounds__(256) k_range_thr(int metric, const float* __restrict__ radius,
+                                                   const float* __restrict__ qinfo, const float* __restrict__ q, int d,
+                                                   int nq, float xmax, float gamma, u64* __restrict__ thr0) {
+    const int qi = blockIdx.x * 256 + threadIdx.x;
+    if (qi >= nq) return;
+    const double r = (double)radius[qi];
+    const double qh = (double)qinfo[2 * qi], dq = (double)qinfo[2 * qi + 1];
+    const double xm = (double)xmax;
+    double eps = ((double)gamma * qh + dq) * xm * 1.01 + 1e-30;
+    double T = r;
+    if (metric == METRIC_L2) {
+        double qq = 0.0;
+        for (int i = 0; i < d; ++i) {
+            const double v = (double)q[(int64_t)qi * d + i];
+            qq += v * v;
+        }
+        const double xe = fmin(xm, (sqrt(qq) + sqrt(fmax(r, 0.0))) * (1.0 + 1e-4));
+        eps = ((double)gamma * qh + dq) * xe * 1.01 + 1e-30;
+        eps = 2.0 * eps + ((double)gamma + 4.0 * 5.9604644775390625e-08) * (xe * xe + 2.0 * xe * qh) * 1.01 +
+              1e-12 * (qq + xe * xe);
+        T = qq - r;
+    }
+    const double lo = T - eps;
+    u64 t = 0ull;  // keep every row
+    if (lo > -3.0e38) {
+        // an fp32 value strictly below lo: the rounded value, two steps down in the key order
+        const uint32_t o = ord_f32((float)fmin(lo, 3.4e38));
+        t = (u64)(o - 2u) << 32;
+    }
+    thr0[qi] = t;
+}
+
+hipError_t launch_range_thr(int metric, const float* radius, const float* qinfo, const float* q, int d, int nq,
+                            float xmax, float gamma, u64* thr0, hipStream_t st) {
+    if (!radius || !qinfo || !q || !thr0 || nq <= 0 || d <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_range_thr, dim3((nq + 255) / 256), dim3(256), 0, st, metric, radius, qinfo, q, d, nq, xmax,
+                       gamma, thr0);
+    return hipGetLastError();
+}
+
+// ---- SCREEN tier: exact refine of the survivors ------------------------------------------------------
+template <int DT, int METRIC, bool QLDS>
+__global__ void __launch_bounds__(FS_THREADS) k_range_refine(RangeArgs a, const u64* __restrict__ glist,
+                                                             const int* __restrict__ gcnt, int lcap) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    double* qs = (double*)smem;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int q = blockIdx.x;
+    const int ng = (a.d + 7) >> 3;
+    constexpr int RR = fs_rows<DT>();
+    if (a.go && a.go[q] == 0) return;
+    const int n = min(max(gcnt[q], 0), lcap);
+    const float* qv = a.q + (int64_t)q * a.d;
+    rs_stage_query<QLDS>(qs, qv, a.d, ng);
+    __syncthreads();
+    const u64* keys = glist + (size_t)q * lcap;
+    const float rq = a.radius[q];
+    const int64_t off = a.off[q], cap = a.cap[q];
+    for (int j0 = (int)blockIdx.y * FS_NW * RR; j0 < n; j0 += (int)gridDim.y * FS_NW * RR) {
+        int64_t rr[RR];
+        int first = -1;
+#pragma unroll
+        for (int i = 0; i < RR; ++i) {
+            const int j = j0 + wid + i * FS_NW;
+            rr[i] = -1;
+            if (j < n) {
+                const u64 key = keys[j];
+                const int64_t id = (int64_t)key_id(key);
+                if (key != 0ull && id < a.n_valid) rr[i] = id;  // (never an address outside the shard)
+            }
+            if (first < 0 && rr[i] >= 0) first = i;
+        }
+        if (first < 0) continue;  // (wave-uniform)
+        if (first > 0) {          // exact_score_rows reads row[0] whatever else is absent
+#pragma unroll
+            for (int i = 1; i < RR; ++i)
+                if (i == first) {
+                    rr[0] = rr[i];
+                    rr[i] = -1;
+                }
+        }
+        double s[RR];
+        exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
+        if (lane == 0) rs_append<METRIC, RR>(a, q, rq, off, cap, rr, s);
+    }
+}
+
+template <int DT>
+static void launch_range_refine_dt(const RangeArgs& a, const u64* glist, const int* gcnt, int lcap, int ny,
+                                   hipStream_t st) {
+    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
+    const bool qlds = qbytes <= RS_QLDS_MAX;
+    const size_t lds = qlds ? qbytes : 0;
+    const dim3 grid(a.nq, ny);
+    if (a.metric == METRIC_IP) {
+        if (qlds) hipLaunchKernelGGL((k_range_refine<DT, METRIC_IP, true>), grid, dim3(FS_THREADS), lds, st, a, glist, gcnt, lcap);
+        else hipLaunchKernelGGL((k_range_refine<DT, METRIC_IP, false>), grid, dim3(FS_THREADS), lds, st, a, glist, gcnt, lcap);
+    } else {
+        if (qlds) hipLaunchKernelGGL((k_range_refine<DT, METRIC_L2, true>), grid, dim3(FS_THREADS), lds, st, a, glist, gcnt, lcap);
+        else hipLaunchKernelGGL((k_range_refine<DT, METRIC_L2, false>), grid, dim3(FS_THREADS), lds, st, a, glist, gcnt, lcap);
+    }
+}
+
+hipError_t launch_range_refine(const RangeArgs& a, const u64* glist, const int* gcnt, int lcap, int ny,
+                               hipStream_t st) {
+    if (!range_args_ok(a) || !glist || !gcnt || lcap <= 0 || ny < 1 || ny > 65535) return hipErrorInvalidValue;
+    if (a.dt == DT_BF16) launch_range_refine_dt<DT_BF16>(a, glist, gcnt, lcap, ny, st);
+    else if (a.dt == DT_F16) launch_range_refine_dt<DT_F16>(a, glist, gcnt, lcap, ny, st);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ---- emit ------------------------------------------------------------------------------------------
+template <int METRIC>
+__global__ void __launch_bounds__(FS_THREADS) k_range_emit(RangeEmitArgs a) {
+    __shared__ double sc[RS_SORT_MAX];
+    __shared__ uint32_t ids[RS_SORT_MAX];
+    const int tid = threadIdx.x;
+    const RangeSeg sg = a.seg[blockIdx.x];
+    if (sg.n <= 0) return;
+    const double* ps = a.psc[sg.buf & 1] + sg.src;
+    const uint32_t* pi = a.pid[sg.buf & 1] + sg.src;
+    if (sg.n > RS_SORT_MAX) {  // as it is: the host sorts it
+        for (int64_t j = tid; j < sg.n; j += FS_THREADS) {
+            const double s = ps[j];
+            a.S[sg.dst + j] = s;
+            a.D[sg.dst + j] = (float)s;
+            a.I[sg.dst + j] = (int64_t)pi[j] + a.id_offset;
+        }
+        return;
+    }
+    const int n = (int)sg.n;
+    int n2 = 64;
+    while (n2 < n) n2 <<= 1;
+    for (int j = tid; j < n2; j += FS_THREADS) {
+        sc[j] = j < n ? ps[j] : (METRIC == METRIC_IP ? -INFINITY : INFINITY);
+        ids[j] = j < n ? pi[j] : 0xFFFFFFFFu;
+    }
+    __syncthreads();
+    sort_valid_best_first<METRIC>(sc, ids, n, n2);
+    for (int j = tid; j < n; j += FS_THREADS) {
+        a.S[sg.dst + j] = sc[j];
+        a.D[sg.dst + j] = (float)sc[j];
+        a.I[sg.dst + j] = (int64_t)ids[j] + a.id_offset;
+    }
+}
+
+hipError_t launch_range_emit(const RangeEmitArgs& a, int nq, hipStream_t st) {
+    if (nq <= 0 || !a.seg || !a.D || !a.I || !a.S || !a.psc[0] || !a.pid[0]) return hipErrorInvalidValue;
+    if (a.metric == METRIC_IP) hipLaunchKernelGGL(k_range_emit<METRIC_IP>, dim3(nq), dim3(FS_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(k_range_emit<METRIC_L2>, dim3(nq), dim3(FS_THREADS), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace vs

@@ -51,6 +51,41 @@ def pack_allowed(n: int, allowed) -> np.ndarray:
 
 
 SEL_MODES = {"auto": 0, "scan": 1, "overfetch": 2}
+RANGE_MODES = {"auto": 0, "scan": 1, "screen": 2}
+
+
+def range_radius(radius, nq: int) -> np.ndarray:
+    """The per-query fp32 radii of a range search: a scalar is broadcast to ``nq`` values, an array
+    must hold exactly ``nq``; NaN raises ``ValueError`` (``-inf`` / ``+inf`` are legal)."""
+    r = np.asarray(radius, dtype=np.float32)
+    if r.ndim == 0:
+        r = np.full((int(nq),), r, dtype=np.float32)
+    if r.ndim != 1 or r.shape[0] != int(nq):
+        raise ValueError(f"radius must be a scalar or {int(nq)} values, got shape {r.shape}")
+    if np.isnan(r).any():
+        raise ValueError("radius must not be NaN")
+    return np.ascontiguousarray(r)
+
+
+def _take_range_result(L, h, nq: int):
+    """Copy an owned ``vs_range_result`` into numpy arrays (lims, D, I) and free it."""
+    try:
+        if int(L.vs_range_nq(h)) != nq:
+            raise _lib.VsError(_lib.VS_ERR_INTERNAL, "range result holds another number of queries")
+        lims = np.ctypeslib.as_array(ctypes.cast(L.vs_range_lims(h), ctypes.POINTER(ctypes.c_int64)),
+                                     shape=(nq + 1,)).copy()
+        total = int(lims[nq])
+        if total:
+            D = np.ctypeslib.as_array(ctypes.cast(L.vs_range_D(h), ctypes.POINTER(ctypes.c_float)),
+                                      shape=(total,)).copy()
+            I = np.ctypeslib.as_array(ctypes.cast(L.vs_range_I(h), ctypes.POINTER(ctypes.c_int64)),
+                                      shape=(total,)).copy()
+        else:
+            D = np.empty((0,), dtype=np.float32)
+            I = np.empty((0,), dtype=np.int64)
+        return lims, D, I
+    finally:
+        L.vs_range_free(h)
 
 
 class Selector:
@@ -159,6 +194,48 @@ class FlatIndex:
             if own is not None:
                 own.close()
         return D, I
+
+    def range_search(self, q, radius, sel=None, max_total: Optional[int] = None):
+        """faiss ``IndexFlat.range_search``: every row whose fp32 score ``D`` passes ``radius`` (``D >
+        radius`` inner product, ``D < radius`` squared L2; a scalar or one value per query) as
+        ``(lims, D, I)``, query ``i``'s rows at ``[lims[i], lims[i + 1])`` best first -- the first
+        entries of ``search(q, k)``.  ``sel`` as in :meth:`search`; ``max_total`` caps the number of
+        results (beyond it the call raises, naming the count)."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"range_search expects an (nq, {self.d}) array, got {q.shape}")
+        nq = q.shape[0]
+        r = range_radius(radius, nq)
+        cap = 0 if max_total is None else int(max_total)
+        if max_total is not None and cap <= 0:
+            raise ValueError("max_total must be > 0")
+        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
+        s = own or sel
+        h = ctypes.c_void_p()
+        try:
+            if s is not None and s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            check(self._L.vs_range_search(self._h, s._h if s is not None else None, _ptr(q), nq, _ptr(r), cap,
+                                          ctypes.byref(h)))
+        finally:
+            if own is not None:
+                own.close()
+        return _take_range_result(self._L, h, nq)
+
+    def set_range_mode(self, mode: str) -> None:
+        """Force the tier of range searches (``"scan"``, ``"screen"`` where it applies) or let the
+        library choose (``"auto"``); the same bits under every mode (``vs_set_range_mode``)."""
+        if mode not in RANGE_MODES:
+            raise ValueError(f"unknown range mode {mode!r}")
+        check(self._L.vs_set_range_mode(self._h, RANGE_MODES[mode]))
+
+    def range_last_stats(self) -> dict:
+        """The last range search: results, tier taken, queries the scan re-answered after a screen
+        overflow, segments sorted on the host (``vs_range_last_stats``)."""
+        buf = (ctypes.c_int64 * 4)()
+        check(self._L.vs_range_last_stats(self._h, buf, 4))
+        return {"total": int(buf[0]), "tier": {1: "scan", 2: "screen"}.get(int(buf[1]), "none"),
+                "rescanned": int(buf[2]), "host_sorted": int(buf[3])}
 
     def selector(self, allowed) -> Selector:
         """A reusable :class:`Selector` over the rows present now (mask or ids, ``pack_allowed``)."""
@@ -484,6 +561,31 @@ class MultiDeviceFlatIndex:
             check(self._L.vs_multi_search_sel(self._h, _ptr(bitmap), bitmap.shape[0], _ptr(q), q.shape[0], k,
                                               _ptr(D), _ptr(I)))
         return D, I
+
+    def range_search(self, q, radius, sel=None, max_total: Optional[int] = None):
+        """:meth:`FlatIndex.range_search` over all devices (``vs_multi_range_search``): the result
+        equals one index over all rows; ``sel`` as in :meth:`search`."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"range_search expects an (nq, {self.d}) array, got {q.shape}")
+        nq = q.shape[0]
+        r = range_radius(radius, nq)
+        cap = 0 if max_total is None else int(max_total)
+        if max_total is not None and cap <= 0:
+            raise ValueError("max_total must be > 0")
+        bitmap = None
+        if sel is not None:
+            n = self.ntotal
+            if isinstance(sel, MaskSelector):  # rows added after it was made are not selected
+                bitmap = np.zeros(((n + 7) // 8,), dtype=np.uint8)
+                bitmap[: sel.bitmap.shape[0]] = sel.bitmap[: bitmap.shape[0]]
+            else:
+                bitmap = np.ascontiguousarray(pack_allowed(n, sel))
+        h = ctypes.c_void_p()
+        check(self._L.vs_multi_range_search(self._h, _ptr(bitmap) if bitmap is not None else None,
+                                            bitmap.shape[0] if bitmap is not None else 0, _ptr(q), nq, _ptr(r), cap,
+                                            ctypes.byref(h)))
+        return _take_range_result(self._L, h, nq)
 
     def selector(self, allowed) -> MaskSelector:
         """A reusable filter over the rows present now (mask or ids, ``pack_allowed``)."""

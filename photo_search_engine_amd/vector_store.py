@@ -314,6 +314,29 @@ class VectorStore:
             results.append({"metadata": self.metadata[index], "distance": float(distance)})
         return results
 
+    def search_range(self, query_embedding: List[float], radius: float, allowed=None,
+                     max_results: Optional[int] = None) -> List[Dict]:
+        """Every item within a score radius, best first (an addition at the boundary; faiss's
+        ``IndexFlat.range_search``): the items whose ``distance`` -- the value :meth:`search` reports
+        -- is above ``radius`` (inner product / cosine) or below it (L2), exactly, however many there
+        are.  It replaces the reference's cut of a guessed top-``candidate_k`` at its score floors
+        (core/searcher.py:771-843): one call per floor, no ``candidate_k`` to guess.  The guards,
+        the normalisation and the result dicts are :meth:`search`'s; ``allowed`` as there;
+        ``max_results`` keeps the best ``max_results`` of them.  HNSW stores and multi-GPU stores answer
+        through the exact flat path, as filtered calls do."""
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        if len(query_embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
+        if max_results is not None and int(max_results) <= 0:
+            return []
+        sel = None if allowed is None else self._allowed_rows(allowed)
+        lims, distances, indices = self.index.range_search(self._normalize_query(query_embedding), float(radius),
+                                                           sel=sel)
+        n = int(lims[1]) if max_results is None else min(int(lims[1]), int(max_results))
+        return [{"metadata": self.metadata[index], "distance": float(distance)}
+                for distance, index in zip(distances[:n].tolist(), indices[:n].tolist())]
+
     def _allowed_rows(self, allowed):
         """A predicate over the metadata as a boolean mask over the items; selectors, masks and ids pass."""
         if callable(allowed):
