@@ -229,6 +229,10 @@ int64_t vs_full_scan_count(vs_index* index);
 /* pinned host bytes the index holds for vs_search's query / result staging (all contexts); each
  * context stages at most 8 MiB and loops over query chunks beyond that */
 int64_t vs_host_staging_bytes(vs_index* index);
+/* HBM bytes the process holds in library workspaces right now (every index, context, selector
+ * scratch and graph; the stored rows and their screen copies are not counted): back at its earlier
+ * value once the objects made since are destroyed */
+int64_t vs_device_bytes_live(void);
 /* HBM bytes the screen copies hold beyond the stored rows (VS_SCREEN_I8: int8 codes, per-row scale |
  * error norm); 0 for native screens */
 int64_t vs_screen_copy_bytes(vs_index* index);

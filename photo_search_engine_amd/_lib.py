@@ -93,6 +93,7 @@ _SIGS = {
     "vs_set_k1_schedule": (ctypes.c_int, [ctypes.c_int32]),
     "vs_k1_schedule": (ctypes.c_int, []),
     "vs_host_staging_bytes": (_c_i64, [_vp]),
+    "vs_device_bytes_live": (_c_i64, []),
     "vs_screen_copy_bytes": (_c_i64, [_vp]),
     "vs_screen_state": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # id selectors (exact filtered search)

@@ -141,11 +141,9 @@ void vs_hnsw_destroy(vs_hnsw* h) {
     {
         DeviceGuard g(h->device);
         if (h->st) (void)hipStreamSynchronize(h->st);
-        for (DevBuf* b : {&h->offsets, &h->neighbors, &h->cum, &h->vis, &h->qdev, &h->outD, &h->outI, &h->ppos, &h->pval})
-            b->release();
         if (h->st) (void)hipStreamDestroy(h->st);
+        delete h;  // (its buffers go with it, the device current)
     }
-    delete h;
 }
 
 int64_t vs_hnsw_ntotal(const vs_hnsw* h) { return h ? h->n : -1; }
@@ -337,12 +335,10 @@ int vs_hnsw_prune(vs_index* index, int64_t m, const int64_t* nodes, const int32_
                 HIP_CHECK(hipStreamSynchronize(st));
             }
         } catch (...) {
-            (void)hipStreamSynchronize(st);
-            for (DevBuf* b : {&dn, &dc, &dout}) b->release();
+            (void)hipStreamSynchronize(st);  // (the buffers are freed behind it, as the scope unwinds)
             (void)hipStreamDestroy(st);
             throw;
         }
-        for (DevBuf* b : {&dn, &dc, &dout}) b->release();
         HIP_CHECK(hipStreamDestroy(st));
     });
 }

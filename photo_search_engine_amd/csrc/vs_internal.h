@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <atomic>
 #include <stdexcept>
 #include <string>
 
@@ -106,56 +107,126 @@ int guarded(F&& f) {
     }
 }
 
-// device buffer that only grows
+// live bytes of every DevBuf in the process (vs_device_bytes_live)
+inline std::atomic<int64_t> g_dev_bytes_live{0};
+
+// device buffer that only grows; owns its allocation (move-only), freed with its device current
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) {
+        o.p = nullptr;
+        o.bytes = 0;
+    }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            std::swap(p, o.p);
+            std::swap(bytes, o.bytes);
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     void ensure(size_t want) {
         if (want <= bytes) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
+        release();
         HIP_CHECK(hipMalloc(&p, want));
         bytes = want;
+        g_dev_bytes_live.fetch_add((int64_t)want, std::memory_order_relaxed);
     }
     template <typename T>
     T* as() const { return (T*)p; }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) {
+            (void)hipFree(p);
+            g_dev_bytes_live.fetch_sub((int64_t)bytes, std::memory_order_relaxed);
+        }
         p = nullptr;
         bytes = 0;
     }
 };
 
-// two pinned host chunks + their "chunk consumed" events: double buffering of host <-> HBM copies
-struct PinnedPair {
-    float* host[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
+// pinned host staging (grow-only, move-only): pageable hipMemcpyAsync is a staged, blocking copy
+struct HostBuf {
+    void* p = nullptr;
     size_t bytes = 0;
-    void ensure(size_t want) {
-        if (!done[0]) {
-            HIP_CHECK(hipEventCreateWithFlags(&done[0], hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&done[1], hipEventDisableTiming));
+    HostBuf() = default;
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    HostBuf(HostBuf&& o) noexcept : p(o.p), bytes(o.bytes) {
+        o.p = nullptr;
+        o.bytes = 0;
+    }
+    HostBuf& operator=(HostBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            std::swap(p, o.p);
+            std::swap(bytes, o.bytes);
         }
+        return *this;
+    }
+    ~HostBuf() { release(); }
+    void ensure(size_t want) {
         if (want <= bytes) return;
-        release_host();
-        HIP_CHECK(hipHostMalloc((void**)&host[0], want, hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void**)&host[1], want, hipHostMallocDefault));
+        release();
+        HIP_CHECK(hipHostMalloc(&p, want, hipHostMallocDefault));
         bytes = want;
     }
-    void release_host() {
-        for (float*& h : host) {
-            if (h) (void)hipHostFree(h);
-            h = nullptr;
-        }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
         bytes = 0;
+    }
+};
+
+// an event that destroys itself (move-only); empty until create()
+struct DevEvent {
+    hipEvent_t e = nullptr;
+    DevEvent() = default;
+    explicit DevEvent(unsigned flags) { create(flags); }
+    DevEvent(const DevEvent&) = delete;
+    DevEvent& operator=(const DevEvent&) = delete;
+    DevEvent(DevEvent&& o) noexcept : e(o.e) { o.e = nullptr; }
+    DevEvent& operator=(DevEvent&& o) noexcept {
+        if (this != &o) {
+            release();
+            std::swap(e, o.e);
+        }
+        return *this;
+    }
+    ~DevEvent() { release(); }
+    void create(unsigned flags = hipEventDefault) {
+        if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, flags));
+    }
+    void release() {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+// two pinned host chunks + their "chunk consumed" events: double buffering of host <-> HBM copies
+struct PinnedPair {
+    HostBuf chunk[2];
+    DevEvent done[2];
+    float* host(int b) const { return (float*)chunk[b].p; }
+    void ensure(size_t want) {
+        done[0].create(hipEventDisableTiming);
+        done[1].create(hipEventDisableTiming);
+        if (want <= chunk[1].bytes) return;
+        release_host();
+        chunk[0].ensure(want);
+        chunk[1].ensure(want);
+    }
+    void release_host() {
+        for (HostBuf& h : chunk) h.release();
     }
     void release() {
         release_host();
-        for (hipEvent_t& e : done) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
+        for (DevEvent& e : done) e.release();
     }
 };
 

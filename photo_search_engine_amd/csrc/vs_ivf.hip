@@ -69,7 +69,7 @@ struct vs_ivf {
     std::shared_mutex rw;
     std::mutex search_mtx;
     std::atomic<bool> timing{false};
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> tev;
+    std::vector<std::pair<DevEvent, DevEvent>> tev;
     std::vector<double> tbytes;
 };
 
@@ -491,10 +491,10 @@ void search_core(vs_ivf* ix, const float* q_dev, int64_t nq, int k, int nprobe, 
     ix->cand.ensure((size_t)max_grid * IVF_QG * a.cap * sizeof(u64));
     a.cand = ix->cand.as<u64>();
     const bool timing = first_pass && ix->timing.load();  // (re-search rounds are not the timed scan)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevEvent e0, e1;
     if (timing) {
-        HIP_CHECK(hipEventCreate(&e0));
-        HIP_CHECK(hipEventCreate(&e1));
+        e0.create();
+        e1.create();
         HIP_CHECK(hipEventRecord(e0, st));
     }
     // Both scans at once when both have work: the GEMV scan (HBM-bound, 8 small workgroups per CU)
@@ -570,7 +570,7 @@ void search_core(vs_ivf* ix, const float* q_dev, int64_t nq, int k, int nprobe, 
     }
     if (timing) {
         HIP_CHECK(hipEventRecord(e1, st));
-        ix->tev.emplace_back(e0, e1);
+        ix->tev.emplace_back(std::move(e0), std::move(e1));
         ix->tbytes.push_back(bytes);
     }
     // 5. exact refine over each query's candidate list (slots -> user ids)
@@ -727,17 +727,10 @@ int vs_ivf_create(int d, int nlist, int metric, int dtype, int device, vs_ivf** 
 
 void vs_ivf_destroy(vs_ivf* ix) {
     if (!ix) return;
+    vs_index* coarse = ix->coarse;
     {
         DeviceGuard dg(ix->device);
         (void)hipDeviceSynchronize();
-        for (DevBuf* b : {&ix->d_page_off, &ix->d_list_pages, &ix->d_list_n, &ix->tmp_rows, &ix->slots, &ix->assign_ids,
-                          &ix->qdev, &ix->probes, &ix->items, &ix->qp, &ix->qinfo, &ix->cand, &ix->glist, &ix->gcnt,
-                          &ix->cert, &ix->outD, &ix->outI, &ix->rec, &ix->next_item})
-            b->release();
-        for (auto& pr : ix->tev) {
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
-        }
         if (ix->data) (void)hipFree(ix->data);
         if (ix->sqn) (void)hipFree(ix->sqn);
         if (ix->slot_id) (void)hipFree(ix->slot_id);
@@ -747,9 +740,9 @@ void vs_ivf_destroy(vs_ivf* ix) {
             if (a) (void)hipStreamDestroy(a);
         for (hipEvent_t& e : ix->aev)
             if (e) (void)hipEventDestroy(e);
+        delete ix;  // (its buffers and timing events go with it, the device current)
     }
-    vs_destroy(ix->coarse);
-    delete ix;
+    vs_destroy(coarse);
 }
 
 int vs_ivf_set_centroids(vs_ivf* ix, const float* c) {
@@ -987,8 +980,6 @@ int vs_ivf_timing_fetch(vs_ivf* ix, float* ms, double* bytes_scanned, int cap) {
                 if (bytes_scanned) bytes_scanned[count] = ix->tbytes[i];
             }
             ++count;
-            (void)hipEventDestroy(pr.first);
-            (void)hipEventDestroy(pr.second);
         }
         ix->tev.clear();
         ix->tbytes.clear();

@@ -3,7 +3,7 @@
 // alone, + the query-fragment reads, + the MFMAs, the whole loop), and the whole loop under the
 // schedules compared in-process (SCHED 0 / the mid-step barrier, static priority for waves 4-7), each
 // with s_memtime / s_memrealtime stamps per workgroup around the loop, so a launch's time splits
-// into cycles and clock.  Entry: vs_k1_probe (vs_api.hip, include/vs.h).
+// into cycles and clock.  Entry: vs_k1_probe (vs_probe.hip, include/vs.h).
 #include "vs_screen.h"
 
 namespace vs {

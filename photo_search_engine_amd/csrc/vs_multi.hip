@@ -123,10 +123,10 @@ struct MCtx {
     std::vector<hipStream_t> st;
     std::vector<DevBuf> qdev, S, I;           // per device: queries, per-shard lists
     std::vector<DevBuf> floor;                // per device: the two-phase floor (device 0's merged phase-A lists)
-    std::vector<hipEvent_t> ready;            // per device: its lists landed on device 0
+    std::vector<DevEvent> ready;              // per device: its lists landed on device 0
     DevBuf gS, gI, oS, oI, oD;                // device 0: gathered [G][nq][k] lists, merged outputs
     DevBuf fS, fI, fD;                        // device 0: the merged phase-A lists (two-phase step)
-    hipEvent_t floor_ready = nullptr;         // device 0: the floor is merged
+    DevEvent floor_ready;                     // device 0: the floor is merged
     Pool* pool = nullptr;                     // one worker per device
 };
 
@@ -180,15 +180,17 @@ void destroy_ctx(vs_multi* m, MCtx* c) {
     for (int g = 0; g < (int)c->st.size(); ++g) {
         DeviceGuard dg(m->dev[g]);
         if (c->st[g]) (void)hipStreamSynchronize(c->st[g]);
+        // (device g's share of the per-device arrays goes while g is current; the rest, all on
+        // device 0, with the context below)
         for (DevBuf* b : {&c->qdev[g], &c->S[g], &c->I[g], &c->floor[g]}) b->release();
-        if (c->ready[g]) (void)hipEventDestroy(c->ready[g]);
+        c->ready[g].release();
         if (c->st[g]) (void)hipStreamDestroy(c->st[g]);
     }
-    if (!m->dev.empty()) {
-        DeviceGuard dg(m->dev[0]);
-        for (DevBuf* b : {&c->gS, &c->gI, &c->oS, &c->oI, &c->oD, &c->fS, &c->fI, &c->fD}) b->release();
-        if (c->floor_ready) (void)hipEventDestroy(c->floor_ready);
+    if (m->dev.empty()) {
+        delete c;
+        return;
     }
+    DeviceGuard dg(m->dev[0]);
     delete c;
 }
 
@@ -196,7 +198,7 @@ MCtx* make_ctx(vs_multi* m) {
     MCtx* c = new MCtx();
     const int G = m->G;
     c->st.assign(G, nullptr);
-    c->ready.assign(G, nullptr);
+    c->ready.resize(G);
     c->qdev.resize(G);
     c->S.resize(G);
     c->I.resize(G);
@@ -205,11 +207,11 @@ MCtx* make_ctx(vs_multi* m) {
         for (int g = 0; g < G; ++g) {
             DeviceGuard dg(m->dev[g]);
             HIP_CHECK(hipStreamCreateWithFlags(&c->st[g], hipStreamNonBlocking));
-            HIP_CHECK(hipEventCreateWithFlags(&c->ready[g], hipEventDisableTiming));
+            c->ready[g].create(hipEventDisableTiming);
         }
         {
             DeviceGuard dg(m->dev[0]);
-            HIP_CHECK(hipEventCreateWithFlags(&c->floor_ready, hipEventDisableTiming));
+            c->floor_ready.create(hipEventDisableTiming);
         }
         c->pool = new Pool(G);
     } catch (...) {

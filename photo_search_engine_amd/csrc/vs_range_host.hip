@@ -1,0 +1,311 @@
+// vs_range_host.hip -- host side of range search (include/vs.h "range search"; kernels: vs_range.hip).
+#include "vs_index.h"
+
+using namespace vs;
+
+namespace {
+
+// the block's small device arrays and their host mirror (one upload of the leading part per launch)
+struct RangeAuxH {
+    float radius[MFMA_QB];
+    int go[MFMA_QB];
+    unsigned long long cnt[MFMA_QB];
+    int64_t off[MFMA_QB];
+    int64_t cap[MFMA_QB];
+    RangeSeg seg[MFMA_QB];
+};
+static_assert(sizeof(RangeSeg) == 32 && offsetof(RangeAuxH, seg) == 8192, "RangeAuxH layout");
+
+constexpr int64_t kRangePairBytes = 32ll << 20;  // first-pass pair buffer of one block (12 B per pair)
+constexpr int kRangeScanRows = 64;               // rows per workgroup of the scan, at least
+
+struct RangeStats {
+    int64_t total = 0, tier = VS_RANGE_SCAN, rescanned = 0, host_sorted = 0;
+};
+
+bool range_screen_applies(const vs_index* ix, const vs_sel* sel, int nqb) {
+    return !sel && (ix->dtype == DT_BF16 || ix->dtype == DT_F16) && nqb > GEMV_NQ_MAX && nqb <= MFMA_QB;
+}
+
+// One block of <= MFMA_QB device queries: counts[q] = the query's result count; unless count_only,
+// its rows are appended to res (D, I, S) in query order, each query's best first.
+void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int nqb, const float* rad, bool screen,
+                 bool count_only, hipStream_t st, RangeStats& stt, int64_t* counts, vs_range_result* res) {
+    const int64_t nseq = sel ? sel->m : ix->ntotal;
+    // every query of the block gets an equal region of the first-pass buffer (all of its rows when
+    // they fit); a query that finds more is rerun into a region of the size it counted
+    const int64_t capq = count_only ? 0 : std::min<int64_t>(nseq, std::max<int64_t>(1, kRangePairBytes / (12 * nqb)));
+    RangeAuxH h{};
+    c->rng_aux.ensure(sizeof(RangeAuxH));
+    uint8_t* ad = c->rng_aux.as<uint8_t>();
+    c->rng_p[0].ensure((size_t)std::max<int64_t>(1, capq * nqb) * 12);
+    for (int q = 0; q < nqb; ++q) {
+        h.radius[q] = rad[q];
+        h.go[q] = 1;
+        h.cnt[q] = 0;
+        h.off[q] = (int64_t)q * capq;
+        h.cap[q] = capq;
+    }
+    // (h outlives every copy from it: each change of h below follows a stream synchronisation)
+    HIP_CHECK(hipMemcpyAsync(ad, &h, offsetof(RangeAuxH, seg), hipMemcpyHostToDevice, st));
+    RangeArgs a{};
+    a.corpus = ix->data;
+    a.d = ix->d;
+    a.dpad = ix->dpad;
+    a.dt = ix->dtype;
+    a.metric = ix->metric;
+    a.n_valid = ix->ntotal;
+    a.q = qd;
+    a.nq = nqb;
+    a.radius = (const float*)(ad + offsetof(RangeAuxH, radius));
+    a.go = (const int*)(ad + offsetof(RangeAuxH, go));
+    a.cnt = (unsigned long long*)(ad + offsetof(RangeAuxH, cnt));
+    a.off = (const int64_t*)(ad + offsetof(RangeAuxH, off));
+    a.cap = (const int64_t*)(ad + offsetof(RangeAuxH, cap));
+    a.psc = c->rng_p[0].as<double>();
+    a.pid = (uint32_t*)(a.psc + capq * nqb);
+    auto read_counts = [&] {
+        HIP_CHECK(hipMemcpyAsync(h.cnt, a.cnt, sizeof(h.cnt[0]) * nqb, hipMemcpyDeviceToHost, st));
+    };
+    std::vector<char> need((size_t)nqb, 1);
+    int64_t total2 = 0;  // pairs of the second buffer (reruns)
+    if (screen) {
+        // the native MFMA screen of the stored rows as search_block launches it unseeded at depth
+        // MFMA_KP_MAX (the int8 screen setting does not apply), started at the radius' key
+        ScreenArgs s = mfma_screen_base(ix, false);
+        c->qinfo.ensure(sizeof(float) * 2 * MFMA_QB);
+        c->qtile.ensure((size_t)MFMA_QB * ix->dpad * ix->es);
+        c->thr0.ensure(sizeof(u64) * MFMA_QB);
+        mfma_workspace(c, s);
+        s.part = s.glist;
+        HIP_CHECK(launch_pack_qtile(ix->dtype, qd, nqb, ix->d, ix->dpad, c->qtile.as<uint8_t>(), c->qinfo.as<float>(),
+                                    c->gcnt.as<int>(), c->drop.as<u64>(), st));
+        HIP_CHECK(launch_range_thr(ix->metric, a.radius, c->qinfo.as<float>(), qd, ix->d, nqb, xmax_of(ix), gamma_of(ix->d),
+                                   c->thr0.as<u64>(), st));
+        s.thr0 = c->thr0.as<u64>();
+        HIP_CHECK(launch_screen_mfma(ix->dtype, s, c->qtile.as<uint8_t>(), nqb, st));
+        RangeArgs r = a;
+        r.go = nullptr;
+        const int ny = std::max(1, std::min(32, 2 * ix->num_cu / nqb));
+        HIP_CHECK(launch_range_refine(r, s.glist, s.gcnt, s.lcap, ny, st));
+        std::vector<u64> drop_h((size_t)nqb), thr_h((size_t)nqb);
+        read_counts();
+        HIP_CHECK(hipMemcpyAsync(drop_h.data(), s.drop, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(thr_h.data(), s.thr0, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        // overflow: a workgroup compacted the query's buffer and may have cut rows above the
+        // threshold -- its list may be incomplete, so the scan answers it (as does a query whose
+        // passing rows outgrew its region)
+        for (int q = 0; q < nqb; ++q) {
+            need[q] = (drop_h[q] > thr_h[q] || (!count_only && (int64_t)h.cnt[q] > capq)) ? 1 : 0;
+            stt.rescanned += need[q];
+        }
+        stt.tier = VS_RANGE_SCREEN;
+    }
+    if (std::any_of(need.begin(), need.end(), [](char v) { return v != 0; })) {
+        for (int q = 0; q < nqb; ++q) {
+            h.go[q] = need[q];
+            if (need[q]) h.cnt[q] = 0;
+        }
+        HIP_CHECK(hipMemcpyAsync(ad, &h, offsetof(RangeAuxH, off), hipMemcpyHostToDevice, st));
+        const int64_t ranges = (nseq + kRangeScanRows - 1) / kRangeScanRows;
+        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ix->num_cu, ranges));
+        // a short sequence, or few workgroups per CU: deal the queries over slices of the grid
+        const int qy = std::max(1, std::min(nqb, 4 * ix->num_cu / G));
+        const uint32_t* ids = sel ? sel->ids : nullptr;
+        const int64_t m = sel ? sel->m : 0;
+        HIP_CHECK(launch_range_scan(a, G, qy, ids, m, st));
+        read_counts();
+        HIP_CHECK(hipStreamSynchronize(st));
+        std::vector<int> over;
+        if (!count_only)
+            for (int q = 0; q < nqb; ++q)
+                if (need[q] && (int64_t)h.cnt[q] > capq) over.push_back(q);
+        if (!over.empty()) {
+            std::vector<int64_t> want((size_t)nqb, 0);
+            for (int q = 0; q < nqb; ++q) h.go[q] = 0;
+            for (int q : over) {
+                want[q] = (int64_t)h.cnt[q];
+                h.go[q] = 1;
+                h.cnt[q] = 0;
+                h.off[q] = total2;
+                h.cap[q] = want[q];
+                total2 += want[q];
+                need[q] = 2;  // (its pairs are in the second buffer)
+            }
+            c->rng_p[1].ensure((size_t)total2 * 12);
+            HIP_CHECK(hipMemcpyAsync(ad, &h, offsetof(RangeAuxH, seg), hipMemcpyHostToDevice, st));
+            RangeArgs a2 = a;
+            a2.psc = c->rng_p[1].as<double>();
+            a2.pid = (uint32_t*)(a2.psc + total2);
+            HIP_CHECK(launch_range_scan(a2, G, qy, ids, m, st));
+            read_counts();
+            HIP_CHECK(hipStreamSynchronize(st));
+            for (int q : over)
+                if ((int64_t)h.cnt[q] != want[q]) throw VsError(VS_ERR_INTERNAL, "range scan: a rerun counted differently");
+        }
+    }
+    int64_t total = 0;
+    for (int q = 0; q < nqb; ++q) {
+        counts[q] = (int64_t)h.cnt[q];
+        total += counts[q];
+    }
+    if (count_only || total == 0) return;
+    for (int q = 0; q < nqb; ++q) {
+        h.seg[q].src = need[q] == 2 ? h.off[q] : (int64_t)q * capq;
+        h.seg[q].n = counts[q];
+        h.seg[q].dst = q == 0 ? 0 : h.seg[q - 1].dst + h.seg[q - 1].n;
+        h.seg[q].buf = need[q] == 2 ? 1 : 0;
+        h.seg[q].pad = 0;
+    }
+    HIP_CHECK(hipMemcpyAsync(ad + offsetof(RangeAuxH, seg), h.seg, sizeof(RangeSeg) * nqb, hipMemcpyHostToDevice, st));
+    c->rng_D.ensure((size_t)total * sizeof(float));
+    c->rng_I.ensure((size_t)total * sizeof(int64_t));
+    c->rng_S.ensure((size_t)total * sizeof(double));
+    RangeEmitArgs e{};
+    e.psc[0] = c->rng_p[0].as<double>();
+    e.pid[0] = (const uint32_t*)(e.psc[0] + capq * nqb);
+    e.psc[1] = c->rng_p[1].as<double>();
+    e.pid[1] = total2 ? (const uint32_t*)(e.psc[1] + total2) : nullptr;
+    e.seg = (const RangeSeg*)(ad + offsetof(RangeAuxH, seg));
+    e.metric = ix->metric;
+    e.id_offset = 0;
+    e.D = c->rng_D.as<float>();
+    e.I = c->rng_I.as<int64_t>();
+    e.S = c->rng_S.as<double>();
+    HIP_CHECK(launch_range_emit(e, nqb, st));
+    const size_t base = res->D.size();
+    res->D.resize(base + (size_t)total);
+    res->I.resize(base + (size_t)total);
+    res->S.resize(base + (size_t)total);
+    HIP_CHECK(hipMemcpyAsync(res->D.data() + base, e.D, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(res->I.data() + base, e.I, (size_t)total * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(res->S.data() + base, e.S, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    // segments past the LDS sort come as they were appended: the same order on the host
+    const bool ip = ix->metric == METRIC_IP;
+    for (int q = 0; q < nqb; ++q) {
+        const int64_t n = counts[q];
+        if (n <= RS_SORT_MAX) continue;
+        ++stt.host_sorted;
+        const size_t o = base + (size_t)h.seg[q].dst;
+        std::vector<int64_t> perm((size_t)n);
+        for (int64_t j = 0; j < n; ++j) perm[j] = j;
+        const double* S = res->S.data() + o;
+        const int64_t* I = res->I.data() + o;
+        std::sort(perm.begin(), perm.end(), [&](int64_t x, int64_t y) {
+            if (S[x] != S[y]) return ip ? S[x] > S[y] : S[x] < S[y];
+            return I[x] < I[y];
+        });
+        std::vector<double> s2((size_t)n);
+        std::vector<int64_t> i2((size_t)n);
+        for (int64_t j = 0; j < n; ++j) {
+            s2[j] = S[perm[j]];
+            i2[j] = I[perm[j]];
+        }
+        for (int64_t j = 0; j < n; ++j) {
+            res->S[o + j] = s2[j];
+            res->I[o + j] = i2[j];
+            res->D[o + j] = (float)s2[j];
+        }
+    }
+}
+
+void range_note_stats(vs_index* ix, const RangeStats& s) {
+    std::lock_guard<std::mutex> g(ix->range_mu);
+    ix->range_stats[0] = s.total;
+    ix->range_stats[1] = s.tier;
+    ix->range_stats[2] = s.rescanned;
+    ix->range_stats[3] = s.host_sorted;
+}
+
+
+}  // namespace
+
+void vs::range_search_host(vs_index* ix, const vs_sel* sel, const float* q, int64_t nq, const float* radius,
+                           int64_t max_total, vs_range_result* out) {
+    check_index(ix);
+    if (nq < 0) throw VsError(VS_ERR_ARG, "nq must be >= 0");
+    std::shared_lock<std::shared_mutex> lk(ix->rw);
+    if (sel) check_sel(ix, sel);
+    out->lims.assign((size_t)nq + 1, 0);
+    out->D.clear();
+    out->I.clear();
+    out->S.clear();
+    RangeStats stt;
+    if (nq == 0) {
+        range_note_stats(ix, stt);
+        return;
+    }
+    if (!q || !radius) throw VsError(VS_ERR_ARG, "null host buffer");
+    for (int64_t i = 0; i < nq; ++i)
+        if (std::isnan(radius[i])) throw VsError(VS_ERR_ARG, "radius is NaN (query " + std::to_string(i) + ")");
+    if (ix->ntotal == 0 || (sel && sel->m == 0)) {  // nothing to return
+        range_note_stats(ix, stt);
+        return;
+    }
+    DeviceGuard dg(ix->device);
+    CtxLease L(ix, nullptr, true);
+    Ctx* c = L.c;
+    hipStream_t st = c->stream;
+    // AUTO: the screen where it applies, otherwise the scan.  (vs_set_scan_limit's rule -- one or two
+    // queries over a small index take the scan alone -- names blocks the screen never serves.)
+    const int mode = ix->range_mode.load();
+    int64_t counts[MFMA_QB];
+    int64_t total = 0;
+    for (int64_t q0 = 0; q0 < nq; q0 += MFMA_QB) {
+        const int nqb = (int)std::min<int64_t>(MFMA_QB, nq - q0);
+        // (the previous block synchronised the stream after its copy from hq)
+        stage_queries(ix, c, q, q0, nqb, st);
+        const bool screen = mode != VS_RANGE_SCAN && range_screen_applies(ix, sel, nqb);
+        // past the cap only the count is wanted (the error names it)
+        const bool count_only = max_total > 0 && total > max_total;
+        range_block(ix, c, sel, c->qdev.as<float>(), nqb, radius + q0, screen, count_only, st, stt, counts, out);
+        for (int j = 0; j < nqb; ++j) out->lims[(size_t)(q0 + j + 1)] = out->lims[(size_t)(q0 + j)] + counts[j];
+        total = out->lims[(size_t)(q0 + nqb)];
+    }
+    stt.total = total;
+    range_note_stats(ix, stt);
+    if (max_total > 0 && total > max_total)
+        throw VsError(VS_ERR_ARG, "range search found " + std::to_string(total) + " results, max_total is " +
+                                      std::to_string(max_total));
+}
+
+extern "C" {
+
+int vs_range_search(vs_index* ix, const vs_sel* sel, const float* q, int64_t nq, const float* radius,
+                    int64_t max_total, vs_range_result** out) {
+    return guarded([&] {
+        if (!out) throw VsError(VS_ERR_ARG, "out is null");
+        std::unique_ptr<vs_range_result> r(new vs_range_result());
+        range_search_host(ix, sel, q, nq, radius, max_total, r.get());
+        std::vector<double>().swap(r->S);  // (the fp64 scores serve the multi-device merge only)
+        *out = r.release();
+    });
+}
+
+const int64_t* vs_range_lims(const vs_range_result* r) { return r ? r->lims.data() : nullptr; }
+const float* vs_range_D(const vs_range_result* r) { return r ? r->D.data() : nullptr; }
+const int64_t* vs_range_I(const vs_range_result* r) { return r ? r->I.data() : nullptr; }
+int64_t vs_range_nq(const vs_range_result* r) { return r ? (int64_t)r->lims.size() - 1 : -1; }
+void vs_range_free(vs_range_result* r) { delete r; }
+
+int vs_set_range_mode(vs_index* ix, int mode) {
+    return guarded([&] {
+        check_index(ix);
+        if (mode != VS_RANGE_AUTO && mode != VS_RANGE_SCAN && mode != VS_RANGE_SCREEN)
+            throw VsError(VS_ERR_ARG, "range mode must be VS_RANGE_AUTO, VS_RANGE_SCAN or VS_RANGE_SCREEN");
+        ix->range_mode.store(mode);
+    });
+}
+
+int vs_range_last_stats(vs_index* ix, int64_t* out, int cap) {
+    return guarded([&] {
+        check_index(ix);
+        if (!out || cap < 0) throw VsError(VS_ERR_ARG, "bad stats buffer");
+        std::lock_guard<std::mutex> g(ix->range_mu);
+        for (int i = 0; i < std::min(cap, 4); ++i) out[i] = ix->range_stats[i];
+    });
+}
+
+}  // extern "C"

@@ -47,7 +47,7 @@ def _exact(ix, q, k):
 
 
 def _sample_tiles(tiles, G):
-    """The seed pass's tiles (vs_api.hip search_block_i8): workgroup b of min(G, 512) screens tile
+    """The seed pass's tiles (vs_search.hip seed_pass, from search_block_i8): workgroup b of min(G, 512) screens tile
     b * (tiles // that)."""
     g = min(G, 512)
     return [b * (tiles // g) for b in range(g)]
