@@ -26,7 +26,8 @@
  * in vs_last_error() (thread-local).  No C++ exception crosses the ABI.
  *
  * Threading: concurrent vs_search* calls on one handle are safe (shared corpus, one stream +
- * workspace per call from a pool).  vs_add, vs_add_device, vs_add_synthetic and vs_reset take an exclusive lock.
+ * workspace per call from a pool).  vs_add, vs_add_device, vs_add_synthetic, vs_reset and vs_remove_ids
+ * take an exclusive lock.
  */
 #ifndef VS_H_
 #define VS_H_
@@ -255,8 +256,8 @@ int vs_screen_state(vs_index* index, double* out, int cap);
  * vs_sel_create stands for faiss.IDSelectorBitmap(n, bitmap): id i is allowed iff
  * (bitmap[i >> 3] >> (i & 7)) & 1 (np.packbits(mask, bitorder="little")).  The selector covers rows
  * [0, n_sel), n_sel = the index's ntotal at creation: nbytes < ceil(n_sel / 8) is VS_ERR_ARG, bits
- * at or past n_sel are ignored, rows added later are not selected, and after vs_reset the selector
- * is stale (searching with it is VS_ERR_ARG).  Creation uploads the bitmap and compacts it once to
+ * at or past n_sel are ignored, rows added later are not selected, and after vs_reset (or a
+ * vs_remove_ids that removed a row) the selector is stale (searching with it is VS_ERR_ARG).  Creation uploads the bitmap and compacts it once to
  * an ascending id list on the device; the selector is then reused across searches (the searcher's
  * relaxation rounds repeat one filter).  It takes the index's shared lock, as searches do. */
 typedef struct vs_sel vs_sel;
@@ -280,6 +281,29 @@ int vs_set_sel_mode(vs_index* index, int mode);
 /* the last filtered search on this handle, up to `cap` (4) values: {m, tier taken (VS_SEL_SCAN /
  * VS_SEL_OVERFETCH), k' (0 for the scan), queries re-answered by the scan} */
 int vs_sel_last_stats(vs_index* index, int64_t* out, int cap);
+
+/* ==== row removal ============================================================================
+ * faiss IndexFlat::remove_ids(IDSelectorBitmap(n, bitmap)): bit i set = remove row i.  Surviving
+ * rows keep their order and take ids 0..ntotal'-1.  *n_removed (may be NULL) = rows removed.
+ * The reference never calls it -- its indexer only appends (core/indexer.py:763), its searcher drops
+ * hits whose file is gone after the search (core/searcher.py:948, :1142) and the only cure is the
+ * full rebuild of force_rebuild (core/indexer.py:667-700) -- but its metadata list is indexed by
+ * faiss id, which is exactly the shift this call makes.
+ *
+ * After the call the index is indistinguishable, through every entry point, from one built by
+ * vs_add of the surviving rows in order (the stored rows, their norms and the int8 screen copy are
+ * compacted in HBM: DESIGN.md §7e).  The bitmap has vs_sel_create's layout: nbytes <
+ * ceil(ntotal / 8) is VS_ERR_ARG, bits at or past ntotal are ignored.  A call that removes nothing
+ * changes and invalidates nothing.  One that removes a row makes every selector and every vs_hnsw
+ * made before it stale (VS_ERR_ARG when used, as after vs_reset).  vs_capacity never changes; with
+ * every row removed ntotal is 0.  The call takes the exclusive lock and waits for the device
+ * (searches queued by the device API included) before the first row moves.  Its bounce buffer is
+ * allocated before anything moves (VS_ERR_OOM leaves the index untouched), is counted in
+ * vs_device_bytes_live and is freed before the call returns. */
+int vs_remove_ids(vs_index* index, const uint8_t* bitmap, int64_t nbytes, int64_t* n_removed);
+/* process-wide: bytes of the bounce buffer a removal may hold (default 256 MiB, floor one row tile:
+ * any smaller value, down to 1, means one tile; < 1 is VS_ERR_ARG) */
+int vs_set_remove_staging_bytes(int64_t bytes);
 
 /* ==== range search: every row within a score radius ==========================================
  * faiss IndexFlat::range_search(x, radius) -> (lims, D, I).  The reference cuts a guessed top-k at
@@ -433,7 +457,9 @@ int vs_ivf_last_search_stats(const vs_ivf* ivf, int* mfma_lists, int* uncertifie
  * one workgroup per query, with the flat path's exact canonical scores as distances: D = scores
  * (IP) / squared distances (L2) best first, I = row ids, -1 padded.  The graph covers the first
  * n rows of the index: rows added behind it are not reachable (the caller searches them exactly
- * and merges); an index holding fewer than n rows is VS_ERR_ARG; max(ef_search, k) <= 2048. */
+ * and merges); an index holding fewer than n rows is VS_ERR_ARG; max(ef_search, k) <= 2048.  A graph
+ * is stale once the index was reset or rows were removed from it (vs_reset, vs_remove_ids: node i is
+ * no longer row i): vs_hnsw_search and vs_hnsw_patch on it are VS_ERR_ARG. */
 typedef struct vs_hnsw vs_hnsw;
 
 int vs_hnsw_create(vs_index* index, int64_t n, const int32_t* levels, const uint64_t* offsets,

@@ -104,6 +104,9 @@ _SIGS = {
     "vs_set_sel_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "vs_sel_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_multi_search_sel": (ctypes.c_int, [_vp, _vp, _c_i64, _vp, _c_i64, ctypes.c_int32, _vp, _vp]),
+    # row removal
+    "vs_remove_ids": (ctypes.c_int, [_vp, _vp, _c_i64, ctypes.POINTER(_c_i64)]),
+    "vs_set_remove_staging_bytes": (ctypes.c_int, [_c_i64]),
     # range search
     "vs_range_search": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _vp, _c_i64, ctypes.POINTER(_vp)]),
     "vs_range_lims": (_vp, [_vp]),

@@ -25,6 +25,7 @@ struct vs_hnsw {
     vs_index* ix = nullptr;  // not owned
     int device = 0;
     int64_t n = 0;
+    uint64_t gen = 0;  // the index's generation at creation (flat_generation)
     int entry = -1, max_level = -1, nbmax = 1;
     DevBuf offsets, neighbors, cum, vis, qdev, outD, outI, ppos, pval;
     std::vector<int32_t> levels_h, cum_h;  // host copies: vs_hnsw_patch validates against them
@@ -38,6 +39,12 @@ namespace {
 constexpr size_t kVisitedBytes = 256u << 20;  // visited bitmaps of one query chunk
 
 void fail(const std::string& m) { throw VsError(VS_ERR_ARG, "hnsw graph: " + m); }
+
+// node i is row i only while the index keeps its rows in place (the search checks under the index's
+// lock; a patch reads no row, so it checks unlocked)
+void check_fresh(const vs_hnsw* h) {
+    if (h->gen != flat_generation(h->ix)) fail("stale (the index was reset or rows were removed after it was made)");
+}
 
 // validate a faiss-layout graph and return its neighbour array with every list cut at its first
 // -1 and later duplicates dropped (-1 padded): both leave every faiss search unchanged
@@ -111,6 +118,7 @@ int vs_hnsw_create(vs_index* index, int64_t n, const int32_t* levels, const uint
             h->ix = index;
             h->device = fv.device;
             h->n = n;
+            h->gen = flat_generation(index);
             h->entry = n ? entry_point : -1;
             h->max_level = n ? max_level : -1;
             h->nbmax = nbmax;
@@ -153,6 +161,7 @@ int vs_hnsw_patch(vs_hnsw* h, int64_t m, const uint64_t* pos, const int32_t* val
     return guarded([&] {
         if (!h || m < 0 || (m > 0 && (!pos || !val))) throw VsError(VS_ERR_ARG, "vs_hnsw_patch: bad arguments");
         const int64_t n = h->n;
+        check_fresh(h);
         if (n == 0) {
             if (m > 0) fail("an empty graph has no neighbour slots");
             return;
@@ -235,8 +244,9 @@ int vs_hnsw_search(vs_hnsw* h, const float* q, int64_t nq, int32_t k, int32_t ef
         std::lock_guard<std::mutex> lk(h->mtx);
         std::shared_lock<std::shared_mutex> rl(flat_lock(h->ix));
         const FlatView fv = flat_view(h->ix);
-        // rows are append-only, so a graph over the first h->n rows stays valid while rows are
-        // added behind it (the host searches those exactly and merges); fewer rows = a reset index
+        check_fresh(h);
+        // rows are only appended within a generation, so a graph over the first h->n rows stays valid
+        // while rows are added behind it (the host searches those exactly and merges)
         if (fv.ntotal < h->n)
             throw VsError(VS_ERR_ARG, "vs_hnsw_search: the graph covers " + std::to_string(h->n) +
                                           " rows, the index holds only " + std::to_string(fv.ntotal));

@@ -1,5 +1,6 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
-// (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_probe.hip, vs_api.hip).
+// (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_probe.hip, vs_api.hip,
+// vs_remove.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -156,6 +157,14 @@ namespace vs {
 // (freed by vs_destroy)
 Ctx* acquire_ctx(vs_index* ix);
 void release_ctx(vs_index* ix, Ctx* c);
+
+// vs_store.hip, shared with vs_remove.hip (the caller holds the exclusive lock, the device current).
+// quantize_rows: the int8 screen copy of rows [r0, r0 + n) once they are in place, stream-ordered
+// on st; with group residuals the groups they fall in get their means recomputed over every row
+// below r0 + n and are requantised from their first row.  refresh_maxsq: the host copies of the
+// device maxima (synchronises the ingest stream).
+void quantize_rows(vs_index* ix, int64_t r0, int64_t n, hipStream_t st);
+void refresh_maxsq(vs_index* ix);
 
 // A leased context works on `st` (null = the context's own stream): the lease first orders `st`
 // behind the previous lease's work, and on release records the context's idle event on `st`.

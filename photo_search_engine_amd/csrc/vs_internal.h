@@ -467,6 +467,23 @@ struct SelTakeArgs {
 };
 hipError_t launch_sel_take(const SelTakeArgs& a, int nq, hipStream_t st);
 
+// ---- row removal (vs_remove.hip) ---------------------------------------------------
+// bits[w] = ~bits[w] for the nwords words of a device bitmap (removed rows -> kept rows; the
+// compaction masks the bits at or past the row count)
+hipError_t launch_remove_complement(uint64_t* bits, int64_t nwords, hipStream_t st);
+// destination tiles [t0, t0 + nt) of the compacted shard, written into the bounce buffer as final
+// tiles: new row j = old row src[j] (ascending, src[j] >= j, j < n_new; the rows of the last tile
+// at or past n_new are zeroed).  A row is nchunks 128 B lines (tile_bytes = nchunks * TR * CHB);
+// sqn_out [nt * TR] receives sqn[src[j]] alongside (0 past n_new).
+hipError_t launch_remove_gather(const uint8_t* data, int64_t tile_bytes, int nchunks, const uint32_t* src,
+                                int64_t n_new, int64_t t0, int64_t nt, uint8_t* stage, const float* sqn,
+                                float* sqn_out, hipStream_t st);
+// the bounce buffer over tiles [t0, t0 + nt) of the shard, and its sqn entries over theirs
+hipError_t launch_remove_place(const uint8_t* stage, int64_t tile_bytes, int64_t t0, int64_t nt, uint8_t* data,
+                               const float* sqn_stage, float* sqn, hipStream_t st);
+// *maxsq = max(*maxsq, bits of max sqn[0, n)) (the caller zeroes it first)
+hipError_t launch_remove_maxsq(const float* sqn, int64_t n, unsigned* maxsq, hipStream_t st);
+
 // ---- range search (vs_range.hip) ---------------------------------------------------------------
 // Every row whose fp32 score D = (float)S passes a per-query radius (D > r inner product, D < r L2),
 // collected as (S, id) pairs in per-query regions of a pair buffer: query q appends at
@@ -603,6 +620,9 @@ struct FlatView {
 };
 FlatView flat_view(vs_index* ix);
 std::shared_mutex& flat_lock(vs_index* ix);
+// bumped by vs_reset and by a vs_remove_ids that removed a row: row i of a handle stamped with an
+// earlier value (selectors, graphs) is no longer row i
+uint64_t flat_generation(vs_index* ix);
 
 // Host <-> HBM row streaming through two pinned host chunks (bulk add, persistence).
 // add_rows_host appends n rows: fill(r0, m, dst) writes rows r0..r0+m-1 (fp32, row-major) into a

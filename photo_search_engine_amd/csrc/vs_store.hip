@@ -125,10 +125,12 @@ void ensure_capacity_i8(vs_index* ix) {
     ix->cap8 = ncap;
 }
 
+}  // namespace
+
 // int8 screen copy of rows [r0, r0 + n) once they are packed (stream-ordered after the pack).  With
 // group residuals, the groups the rows fall in get their means (re)computed over every row they
 // hold now, and their rows are (re)quantised from the group's first row.
-void quantize_rows(vs_index* ix, int64_t r0, int64_t n, hipStream_t st) {
+void vs::quantize_rows(vs_index* ix, int64_t r0, int64_t n, hipStream_t st) {
     if (ix->screen != VS_SCREEN_I8 || n <= 0) return;
     if (ix->gmean) {
         // rows already searchable get new codes, bounds and group means: searches still queued on
@@ -146,7 +148,7 @@ void quantize_rows(vs_index* ix, int64_t r0, int64_t n, hipStream_t st) {
                                 ix->d_maxsq + 2, st, ix->gmean));
 }
 
-void refresh_maxsq(vs_index* ix) {
+void vs::refresh_maxsq(vs_index* ix) {
     unsigned bits[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     HIP_CHECK(hipMemcpyAsync(bits, ix->d_maxsq, sizeof(bits), hipMemcpyDeviceToHost, ix->own));
     HIP_CHECK(hipStreamSynchronize(ix->own));
@@ -155,10 +157,8 @@ void refresh_maxsq(vs_index* ix) {
     ix->i8_res = ix->gmean != nullptr && bits[6] != 0;  // some group coded against its mean
 }
 
-
-}  // namespace
-
 unsigned* vs::full_scan_counter(vs_index* ix) { return ix->d_unres; }
+uint64_t vs::flat_generation(vs_index* ix) { return ix->reset_gen.load(); }
 
 void vs::truncate_rows(vs_index* ix, int64_t n) {
     check_index(ix);

@@ -91,7 +91,8 @@ def _take_range_result(L, h, nq: int):
 class Selector:
     """A set of row ids of one :class:`FlatIndex` (``vs_sel``, include/vs.h): faiss's
     ``IDSelectorBitmap`` uploaded and compacted once, reused across searches.  It covers the rows
-    present when it was made (rows added later are not selected) and is stale after ``reset()``."""
+    present when it was made (rows added later are not selected) and is stale after ``reset()`` or a
+    ``remove_ids`` that removed a row."""
 
     def __init__(self, index: "FlatIndex", allowed) -> None:
         self._h = None
@@ -282,6 +283,23 @@ class FlatIndex:
 
     def reset(self) -> None:
         check(self._L.vs_reset(self._h))
+
+    def remove_ids(self, ids_or_mask) -> int:
+        """faiss ``IndexFlat.remove_ids``: remove the given rows (a boolean mask over the rows or row
+        ids, as :func:`pack_allowed` takes them) and return how many went.  The surviving rows keep
+        their order and take ids ``0..ntotal-1``; the index then equals one built by ``add`` of the
+        survivors.  A call that removes a row makes earlier :class:`Selector` objects and HNSW graphs
+        stale (include/vs.h ``vs_remove_ids``); the capacity is kept."""
+        return self.remove_bitmap(pack_allowed(self.ntotal, ids_or_mask))
+
+    def remove_bitmap(self, bitmap) -> int:
+        """:meth:`remove_ids` from a packed bitmap (``pack_allowed``'s layout, bit set = remove; bits
+        past ``ntotal`` are ignored, a bitmap shorter than ``ceil(ntotal / 8)`` bytes is an argument
+        error)."""
+        bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8)
+        removed = ctypes.c_int64(0)
+        check(self._L.vs_remove_ids(self._h, _ptr(bitmap), bitmap.shape[0], ctypes.byref(removed)))
+        return int(removed.value)
 
     # -- screen selection ----------------------------------------------------------------------
     SCREENS = {"native": 0, "int8": 1}
@@ -477,6 +495,15 @@ def k1_schedule() -> int:
     return int(_lib.load().vs_k1_schedule())
 
 
+REMOVE_STAGING_DEFAULT = 256 << 20
+
+
+def set_remove_staging_bytes(nbytes: int = REMOVE_STAGING_DEFAULT) -> None:
+    """Bytes of the bounce buffer a ``remove_ids`` may hold, process-wide (include/vs.h
+    ``vs_set_remove_staging_bytes``): any value from 1 up, floored at one row tile of the index."""
+    check(_lib.load().vs_set_remove_staging_bytes(int(nbytes)))
+
+
 def synthesize_device(device: int, seed: int, global_row0: int, n: int, d: int, out_ptr: int, normalize: bool = True,
                       dtype: str = "f32", stream: Optional[int] = None) -> None:
     """Write synthetic rows [global_row0, +n) as row-major fp32 (rounded to ``dtype``) to device
@@ -642,6 +669,23 @@ class MultiDeviceFlatIndex:
     def reset(self) -> None:
         self._drop_prune_copy()
         check(self._L.vs_multi_reset(self._h))
+
+    def remove_ids(self, ids_or_mask) -> int:
+        """:meth:`FlatIndex.remove_ids` over the devices, O(N) through the host: rows are dealt to
+        the devices by global id chunk, so the shift crosses devices -- the survivors are read back
+        (``reconstruct_n``), the index is reset and they are added again.  The stored values are
+        what ``add`` stores of them, so the result equals one index built from the survivors."""
+        n = self.ntotal
+        remove = np.unpackbits(pack_allowed(n, ids_or_mask), bitorder="little")[:n].astype(bool)
+        removed = int(remove.sum())
+        if removed == 0:
+            return 0
+        keep = [self.reconstruct_n(r0, min(65536, n - r0))[~remove[r0:r0 + 65536]] for r0 in range(0, n, 65536)]
+        self.reset()
+        for rows in keep:
+            if rows.shape[0]:
+                self.add(np.ascontiguousarray(rows))
+        return removed
 
     def set_screen(self, screen: str) -> None:
         if screen not in FlatIndex.SCREENS:

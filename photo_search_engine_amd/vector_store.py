@@ -43,7 +43,7 @@ import numpy as np
 from . import faiss_format
 from . import hnsw as hnsw_mod
 from .hnsw import HNSWGraph
-from .index import FlatIndex, MultiDeviceFlatIndex
+from .index import FlatIndex, MultiDeviceFlatIndex, pack_allowed
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
@@ -347,7 +347,7 @@ class VectorStore:
     def selector(self, allowed):
         """A reusable selector for :meth:`search`'s ``allowed`` (the searcher's relaxation rounds repeat
         one filter): a boolean mask, item ids, or a predicate applied to each ``self.metadata[i]``.
-        It covers the items present now and is stale after :meth:`clear`."""
+        It covers the items present now and is stale after :meth:`clear` or a removal."""
         if self.index is None:
             raise RuntimeError("the store has no index yet")
         return self.index.selector(self._allowed_rows(allowed))
@@ -656,6 +656,48 @@ class VectorStore:
             photo_path = md.get("photo_path") if isinstance(md, dict) else None
             if isinstance(photo_path, str) and photo_path:
                 self._path_to_index[photo_path] = base + i
+
+    # ------------------------------------------------------------------ removal
+    def remove_ids(self, ids) -> int:
+        """Remove items by id (an addition at the boundary; faiss's ``IndexFlat.remove_ids``): a boolean
+        mask over the items or item ids.  The surviving items keep their order and take ids
+        ``0..n-1`` in the index and in ``metadata`` alike, which is the shift the reference's
+        id-indexed ``metadata`` list needs.  Returns the number removed.  An HNSW graph is dropped,
+        not edited (the next save or graph search builds one over the survivors, as a fresh store
+        would), and the next :meth:`save` rewrites the whole index file: a shrink in place could not
+        keep the header-last guarantee of the append path."""
+        if self.index is None:
+            return 0
+        n = int(self.index.ntotal)
+        remove = np.unpackbits(pack_allowed(n, ids), bitorder="little")[:n].astype(bool)  # (validates ids / mask)
+        if not remove.any():
+            return 0
+        removed = int(self.index.remove_ids(remove))
+        new_id = np.cumsum(~remove) - 1  # surviving item i -> its new id
+        self.metadata = [m for m, gone in zip(self.metadata, remove.tolist()) if not gone]
+        self._embeddings = {int(new_id[i]): v for i, v in self._embeddings.items() if i < n and not remove[i]}
+        self._rebuild_path_index()
+        self._drop_graph()
+        self._persisted = None
+        return removed
+
+    def remove_items(self, photo_paths) -> int:
+        """Remove the items with these ``photo_path`` values (unknown paths are ignored); returns the
+        number removed.  The indexer's prune of files that vanished from disk."""
+        ids = sorted({self._path_to_index[p] for p in photo_paths if p in self._path_to_index})
+        return self.remove_ids(np.asarray(ids, dtype=np.int64)) if ids else 0
+
+    def update_item(self, embedding: List[float], metadata: Dict) -> None:
+        """Replace the item with ``metadata["photo_path"]`` if the store holds one, then
+        :meth:`add_item`: the new row goes to the end, as faiss's remove + add leaves it."""
+        if embedding is None:
+            raise ValueError("向量不能为空")
+        if self.dimension is not None and len(embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(embedding)} != {self.dimension}")
+        photo_path = metadata.get("photo_path")
+        if isinstance(photo_path, str) and photo_path in self._path_to_index:
+            self.remove_items([photo_path])
+        self.add_item(embedding, metadata)
 
     def search_batch(self, queries: np.ndarray, top_k: int) -> Tuple[np.ndarray, np.ndarray]:
         """Batched search in faiss layout: (D nq x k float32, I nq x k int64), rows normalised
