@@ -347,6 +347,42 @@ int vs_set_range_mode(vs_index* index, int mode);
  * overflow, queries whose segment (longer than 4096 rows) was sorted on the host} */
 int vs_range_last_stats(vs_index* index, int64_t* out, int cap);
 
+/* ==== queries taken from stored rows ==========================================================
+ * "What looks like this photo" and "which photos are near-duplicates" ask the index about rows it
+ * already holds.  The reference reconstructs the row to a Python list, searches max(k + 1, 5 k) rows
+ * and throws its own photo out by path afterwards (core/searcher.py:1751-1814 search_by_image_path);
+ * its _deduplicate_results merges equal paths only.  In these two calls the queries never leave the
+ * device: query i is the stored value of row ids[i] exactly as vs_reconstruct returns it (fp32, exact
+ * for every dtype, not normalised again), gathered in HBM.  ids may repeat and come in any order; an
+ * id outside [0, ntotal) is VS_ERR_ARG, checked before anything is launched (so with an empty index
+ * only n = 0 is legal).  Both calls take the shared lock, as searches do.
+ *
+ * self_mode says what becomes of the query's own row:
+ *   VS_SELF_KEEP   the result is bit-equal to vs_search (sel NULL) / vs_search_sel / vs_range_search
+ *                  on those vectors.
+ *   VS_SELF_DROP   the same, with the entry whose id is ids[i] removed -- by id, not by position: a
+ *                  duplicate with a lower id scores the same as the row itself and comes first.
+ *                  vs_search_rows runs the search at min(k + 1, ntotal); the entry holding ids[i] is
+ *                  taken out and the rest moves up; if the row itself is not among the k + 1 (inner
+ *                  product over unnormalised rows; a row sel does not allow) the last entry goes
+ *                  instead, i.e. the first k stand unchanged; the tail is padded with -1 / -+FLT_MAX as
+ *                  vs_search pads it.  k + 1 is therefore what vs_search's limit applies to.
+ *   VS_SELF_ABOVE  (vs_range_search_rows only; VS_ERR_ARG for vs_search_rows) only rows with id >
+ *                  ids[i] are returned: in a self-join every pair then comes exactly once, as
+ *                  (lower id -> higher id), and the scan reads only the rows that can still pass.
+ *
+ * vs_search_rows: D, I host n x k, as vs_search / vs_search_sel (sel may be NULL); n = 0 returns at
+ * once; a stale selector is VS_ERR_ARG; vs_sel_last_stats reports as for vs_search_sel.
+ * vs_range_search_rows: radius holds n values; ids NULL = rows 0..n-1, and n must then equal ntotal
+ * (the whole-corpus self-join); the removed rows are never counted, so max_total, the error that
+ * names the count and vs_range_last_stats see the filtered answer.  n = 0, a NaN radius, a stale
+ * selector, max_total and the owned result behave as in vs_range_search. */
+enum { VS_SELF_KEEP = 0, VS_SELF_DROP = 1, VS_SELF_ABOVE = 2 };
+int vs_search_rows(vs_index* index, const vs_sel* sel, const int64_t* ids, int64_t n, int32_t k, int32_t self_mode,
+                   float* D, int64_t* I);
+int vs_range_search_rows(vs_index* index, const vs_sel* sel, const int64_t* ids, int64_t n, const float* radius,
+                         int32_t self_mode, int64_t max_total, vs_range_result** out);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

@@ -115,6 +115,9 @@ _SIGS = {
     "vs_set_range_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
     "vs_range_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_multi_range_search": (ctypes.c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _vp, _c_i64, ctypes.POINTER(_vp)]),
+    # queries taken from stored rows
+    "vs_search_rows": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
+    "vs_range_search_rows": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _vp, ctypes.c_int32, _c_i64, ctypes.POINTER(_vp)]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

@@ -1,6 +1,6 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
-// (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_probe.hip, vs_api.hip,
-// vs_remove.hip).
+// (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
+// vs_api.hip, vs_remove.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,6 +44,8 @@ struct Ctx {
     DevBuf rng_p[2];          // range search: the pair buffers (first pass; reruns of overflowed queries)
     DevBuf rng_aux;           // ... the block's radii, go flags, counters, regions and segments
     DevBuf rng_D, rng_I, rng_S;  // ... the block's emitted results
+    DevBuf row_ids;           // queries taken from stored rows: the call's ids, uploaded once
+    DevBuf row_out;           // ... a chunk's lists without the rows themselves ([I int64 | D fp32], k_rows_take)
     DevBuf rsc, rdone;        // split refine: per-query scores + ids of the kept rows, done counters
     DevBuf pa;       // two-phase (sharded) search: the refine's phase-1 state between the launches
     DevBuf rows[2];  // read_rows_host: unpacked fp32 chunks
@@ -268,7 +270,43 @@ void fill_padding(float* D, int64_t* I, int64_t n, float fillD);
 // [m][kk] staged results -> the caller's [..][k] rows from q0 on, padded past kk (faiss layout)
 void scatter_padded(const StagedOut& o, int64_t q0, int64_t m, int k, int kk, float fillD, float* D, int64_t* I);
 
+// vs_search's road from a staged chunk on: the m queries in c->qdev searched at depth kk into so's
+// device block, fetched to its host block, certificate failures re-searched one by one (4x deeper
+// screens, then the exact full scan) into the host block -- and, with mirror, into the device block
+// too (a kernel reads the lists afterwards).  Synchronises st.
+void search_staged(vs_index* ix, Ctx* c, int64_t m, int kk, const StagedOut& so, hipStream_t st, bool mirror);
+
 // ---- vs_sel_host.hip ----
 void check_sel(const vs_index* ix, const vs_sel* sel);
+// the tier of one filtered call (vs_set_sel_mode, the AUTO rule) and its run over one batch of device
+// queries: outputs device [nq][k]; returns the queries the overfetch tier left short and the scan
+// re-answered; synchronises st on that tier.  sel_note_stats files what vs_sel_last_stats reports.
+struct SelPlan {
+    int tier;  // VS_SEL_SCAN / VS_SEL_OVERFETCH
+    int kp;    // the overfetch depth k' (0 for the scan)
+};
+SelPlan sel_plan(const vs_index* ix, const vs_sel* sel, int64_t nq, int k);
+int64_t sel_search_ctx(vs_index* ix, Ctx* c, const vs_sel* sel, const SelPlan& plan, const float* q, int64_t nq, int k,
+                       const SearchOut& out, hipStream_t st);
+void sel_note_stats(vs_index* ix, const vs_sel* sel, const SelPlan& plan, int64_t redo);
+
+// ---- vs_range_host.hip ----
+struct RangeStats {
+    int64_t total = 0, tier = VS_RANGE_SCAN, rescanned = 0, host_sorted = 0;
+};
+// queries taken from stored rows: the block's device array of row ids, VS_SELF_*, and (ABOVE without a
+// selector) the smallest of those ids
+struct RangeSelf {
+    const int64_t* ids = nullptr;
+    int mode = VS_SELF_KEEP;
+    int64_t row0 = 0;
+};
+bool range_screen_applies(const vs_index* ix, const vs_sel* sel, int nqb);
+// One block of <= MFMA_QB device queries: counts[q] = the query's result count; unless count_only,
+// its rows are appended to res (D, I, S) in query order, each query's best first.
+void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int nqb, const float* rad, bool screen,
+                 bool count_only, hipStream_t st, RangeStats& stt, int64_t* counts, vs_range_result* res,
+                 const RangeSelf& self = RangeSelf());
+void range_note_stats(vs_index* ix, const RangeStats& s);
 
 }  // namespace vs

@@ -503,6 +503,14 @@ struct RangeArgs {
     const int64_t* off;     // [nq] first slot of the query's region
     const int64_t* cap;     // [nq] slots of the region (0 = count only)
     unsigned long long* cnt;  // [nq] passing rows found (zeroed by the host before the launch)
+    // queries taken from stored rows (vs_range_search_rows): self[q] = the row query q was gathered
+    // from; VS_SELF_DROP rejects that row, VS_SELF_ABOVE every row with id <= self[q], before it is
+    // counted.  row0 (ABOVE without a selector): no self id of the block is below it, so the scan
+    // tier's sequence is [row0, n_valid).  A value-initialised struct (null, VS_SELF_KEEP, 0) is the
+    // plain range search: it launches the kernels' instantiation that reads none of the three.
+    const int64_t* self;
+    int self_mode;
+    int64_t row0;
 };
 // SCAN tier: G workgroups split the n_valid rows, or the m listed rows ids[0, m) (ascending, each <
 // n_valid) when ids is given; qy (1..nq) query slices deal the block's queries (grid G x qy)
@@ -536,6 +544,22 @@ struct RangeEmitArgs {
 // one workgroup per query: segments of at most RS_SORT_MAX pairs are written best first (S, then
 // the lower id), longer ones as they are (the host sorts them)
 hipError_t launch_range_emit(const RangeEmitArgs& a, int nq, hipStream_t st);
+
+// ---- queries taken from stored rows (vs_rows.hip) -----------------------------------------------
+// exact lists [nq][kk] (best first, -1 padded) -> [nq][k], k <= kk, with the entry whose id is self[q]
+// taken out and the rest moved up; a list that does not hold self[q] keeps its first k entries; slots
+// the list cannot fill are padded as vs_search pads them.  Inputs and outputs must not overlap.
+struct RowsTakeArgs {
+    const int64_t* self;   // [nq] the row each query was gathered from
+    const int64_t* I_in;   // [nq][kk]
+    const float* D_in;     // [nq][kk]
+    const double* S_in;    // [nq][kk] (with S64)
+    int kk, k, metric;
+    float* D;              // [nq][k]
+    int64_t* I;            // [nq][k]
+    double* S64;           // [nq][k] (may be null)
+};
+hipError_t launch_rows_take(const RowsTakeArgs& a, int64_t nq, hipStream_t st);
 
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)

@@ -11,7 +11,10 @@
 //     buffer through a wave-aggregated atomic (the wave's lane 0 holds its rows' scores and adds
 //     their count once); a pair is stored only while its slot is inside the region, the counter
 //     keeps counting past the end, and the host reruns an overflowed query with a region of the
-//     counted size.  No row is scored twice unless its query overflowed.
+//     counted size.  No row is scored twice unless its query overflowed.  Queries taken from stored
+//     rows (vs_range_search_rows) carry their row's id: the row itself (VS_SELF_DROP) or every row
+//     at or below it (VS_SELF_ABOVE) is rejected before it is counted, and under ABOVE without a
+//     selector the workgroups split [row0, n_valid) -- the rows that can still pass -- instead.
 //   * k_range_thr + k_range_refine (SCREEN tier): the native MFMA screen (launch_screen_mfma, as
 //     vs_search launches it) starts at thr0[q], a key below every key a passing row can get (the
 //     proof is at k_range_thr); k_range_refine scores each query's survivors exactly, several rows
@@ -33,14 +36,22 @@ __device__ __forceinline__ bool rs_pass(double S, float r, int metric) {
     return metric == METRIC_IP ? D > r : D < r;
 }
 
+// queries taken from stored rows: may row `id` be returned to the query gathered from row `self`?
+// (mode VS_SELF_KEEP for every plain range search: always)
+__device__ __forceinline__ bool rs_self_ok(int64_t id, int64_t self, int mode) {
+    return mode == VS_SELF_DROP ? id != self : mode == VS_SELF_ABOVE ? id > self : true;
+}
+
 // lane 0 of a wave: append the passing rows among its R scored rows to query q's region
-template <int METRIC, int R>
+// (SELF: the queries are stored rows; without it the self fields are not read and a plain range
+// search compiles to the code it always ran)
+template <int METRIC, int R, bool SELF>
 __device__ __forceinline__ void rs_append(const RangeArgs& a, int q, float rq, int64_t off, int64_t cap,
-                                          const int64_t (&rr)[R], const double (&s)[R]) {
+                                          int64_t self, const int64_t (&rr)[R], const double (&s)[R]) {
     unsigned pass = 0u;
 #pragma unroll
     for (int i = 0; i < R; ++i)
-        if (rr[i] >= 0 && rs_pass(s[i], rq, METRIC)) pass |= 1u << i;
+        if (rr[i] >= 0 && (!SELF || rs_self_ok(rr[i], self, a.self_mode)) && rs_pass(s[i], rq, METRIC)) pass |= 1u << i;
     if (!pass) return;
     unsigned long long pos = atomicAdd(a.cnt + q, (unsigned long long)__popc(pass));
 #pragma unroll
@@ -61,7 +72,7 @@ __device__ __forceinline__ void rs_stage_query(double* qs, const float* qv, int 
 }
 
 // ---- SCAN tier ------------------------------------------------------------------------------------
-template <int DT, int METRIC, bool QLDS, bool SEL>
+template <int DT, int METRIC, bool QLDS, bool SEL, bool SELF>
 __global__ void __launch_bounds__(FS_THREADS) k_range_scan(RangeArgs a, const uint32_t* __restrict__ ids, int64_t m) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     double* qs = (double*)smem;
@@ -69,8 +80,10 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_scan(RangeArgs a, const ui
     const int b = blockIdx.x, G = gridDim.x;
     const int ng = (a.d + 7) >> 3;
     constexpr int RR = fs_rows<DT>();
-    const int64_t nseq = SEL ? m : a.n_valid;
-    const int64_t r0 = nseq * b / G, r1 = nseq * (b + 1) / G;
+    // (a self-join under VS_SELF_ABOVE: rows below row0 pass for no query of the block)
+    const int64_t lo = SEL || !SELF ? 0 : a.row0;
+    const int64_t nseq = SEL ? m : a.n_valid - lo;
+    const int64_t r0 = lo + nseq * b / G, r1 = lo + nseq * (b + 1) / G;
     for (int q = blockIdx.y; q < a.nq; q += gridDim.y) {
         if (a.go && a.go[q] == 0) continue;  // (block-uniform)
         __syncthreads();                     // (the previous query's readers of qs are done)
@@ -79,6 +92,7 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_scan(RangeArgs a, const ui
         __syncthreads();
         const float rq = a.radius[q];
         const int64_t off = a.off[q], cap = a.cap[q];
+        const int64_t self = SELF ? a.self[q] : -1;
         for (int64_t base = r0; base < r1; base += FS_NW * RR) {
             int64_t rr[RR];
 #pragma unroll
@@ -90,7 +104,7 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_scan(RangeArgs a, const ui
             if (rr[0] < 0) continue;  // (wave-uniform)
             double s[RR];
             exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
-            if (lane == 0) rs_append<METRIC, RR>(a, q, rq, off, cap, rr, s);
+            if (lane == 0) rs_append<METRIC, RR, SELF>(a, q, rq, off, cap, self, rr, s);
         }
     }
 }
@@ -98,10 +112,12 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_scan(RangeArgs a, const ui
 template <int DT, int METRIC, bool QLDS>
 static void launch_range_scan_one(const RangeArgs& a, int G, int qy, size_t lds, const uint32_t* ids, int64_t m,
                                   hipStream_t st) {
-    if (ids)
-        hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true>), dim3(G, qy), dim3(FS_THREADS), lds, st, a, ids, m);
-    else
-        hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false>), dim3(G, qy), dim3(FS_THREADS), lds, st, a, ids, m);
+    const bool self = a.self_mode != VS_SELF_KEEP;
+    const dim3 grid(G, qy), block(FS_THREADS);
+    if (ids && self) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true, true>), grid, block, lds, st, a, ids, m);
+    else if (ids) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true, false>), grid, block, lds, st, a, ids, m);
+    else if (self) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false, true>), grid, block, lds, st, a, ids, m);
+    else hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false, false>), grid, block, lds, st, a, ids, m);
 }
 
 template <int DT>
@@ -120,11 +136,14 @@ static void launch_range_scan_dt(const RangeArgs& a, int G, int qy, const uint32
 
 static bool range_args_ok(const RangeArgs& a) {
     return a.corpus && a.q && a.radius && a.off && a.cap && a.cnt && a.psc && a.pid && a.nq > 0 && a.d > 0 &&
-           a.n_valid > 0 && (a.metric == METRIC_IP || a.metric == METRIC_L2);
+           a.n_valid > 0 && (a.metric == METRIC_IP || a.metric == METRIC_L2) &&
+           (a.self_mode == VS_SELF_KEEP || ((a.self_mode == VS_SELF_DROP || a.self_mode == VS_SELF_ABOVE) && a.self)) &&
+           a.row0 >= 0 && a.row0 < a.n_valid;
 }
 
 hipError_t launch_range_scan(const RangeArgs& a, int G, int qy, const uint32_t* ids, int64_t m, hipStream_t st) {
-    if (!range_args_ok(a) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) || (!ids && m != 0))
+    if (!range_args_ok(a) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) || (!ids && m != 0) ||
+        (ids && a.row0 != 0))
         return hipErrorInvalidValue;
     if (a.dt == DT_F32) launch_range_scan_dt<DT_F32>(a, G, qy, ids, m, st);
     else if (a.dt == DT_BF16) launch_range_scan_dt<DT_BF16>(a, G, qy, ids, m, st);
@@ -187,7 +206,7 @@ hipError_t launch_range_thr(int metric, const float* radius, const float* qinfo,
 }
 
 // ---- SCREEN tier: exact refine of the survivors ------------------------------------------------------
-template <int DT, int METRIC, bool QLDS>
+template <int DT, int METRIC, bool QLDS, bool SELF>
 __global__ void __launch_bounds__(FS_THREADS) k_range_refine(RangeArgs a, const u64* __restrict__ glist,
                                                              const int* __restrict__ gcnt, int lcap) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -204,6 +223,7 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_refine(RangeArgs a, const 
     const u64* keys = glist + (size_t)q * lcap;
     const float rq = a.radius[q];
     const int64_t off = a.off[q], cap = a.cap[q];
+    const int64_t self = SELF ? a.self[q] : -1;
     for (int j0 = (int)blockIdx.y * FS_NW * RR; j0 < n; j0 += (int)gridDim.y * FS_NW * RR) {
         int64_t rr[RR];
         int first = -1;
@@ -229,7 +249,7 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_refine(RangeArgs a, const 
         }
         double s[RR];
         exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
-        if (lane == 0) rs_append<METRIC, RR>(a, q, rq, off, cap, rr, s);
+        if (lane == 0) rs_append<METRIC, RR, SELF>(a, q, rq, off, cap, self, rr, s);
     }
 }
 
@@ -239,14 +259,18 @@ static void launch_range_refine_dt(const RangeArgs& a, const u64* glist, const i
     const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
     const bool qlds = qbytes <= RS_QLDS_MAX;
     const size_t lds = qlds ? qbytes : 0;
-    const dim3 grid(a.nq, ny);
-    if (a.metric == METRIC_IP) {
-        if (qlds) hipLaunchKernelGGL((k_range_refine<DT, METRIC_IP, true>), grid, dim3(FS_THREADS), lds, st, a, glist, gcnt, lcap);
-        else hipLaunchKernelGGL((k_range_refine<DT, METRIC_IP, false>), grid, dim3(FS_THREADS), lds, st, a, glist, gcnt, lcap);
-    } else {
-        if (qlds) hipLaunchKernelGGL((k_range_refine<DT, METRIC_L2, true>), grid, dim3(FS_THREADS), lds, st, a, glist, gcnt, lcap);
-        else hipLaunchKernelGGL((k_range_refine<DT, METRIC_L2, false>), grid, dim3(FS_THREADS), lds, st, a, glist, gcnt, lcap);
-    }
+    const dim3 grid(a.nq, ny), block(FS_THREADS);
+    const bool ip = a.metric == METRIC_IP, self = a.self_mode != VS_SELF_KEEP;
+#define VS_RANGE_REFINE(M, Q, S) hipLaunchKernelGGL((k_range_refine<DT, M, Q, S>), grid, block, lds, st, a, glist, gcnt, lcap)
+    if (ip && qlds && self) VS_RANGE_REFINE(METRIC_IP, true, true);
+    else if (ip && qlds) VS_RANGE_REFINE(METRIC_IP, true, false);
+    else if (ip && self) VS_RANGE_REFINE(METRIC_IP, false, true);
+    else if (ip) VS_RANGE_REFINE(METRIC_IP, false, false);
+    else if (qlds && self) VS_RANGE_REFINE(METRIC_L2, true, true);
+    else if (qlds) VS_RANGE_REFINE(METRIC_L2, true, false);
+    else if (self) VS_RANGE_REFINE(METRIC_L2, false, true);
+    else VS_RANGE_REFINE(METRIC_L2, false, false);
+#undef VS_RANGE_REFINE
 }
 
 hipError_t launch_range_refine(const RangeArgs& a, const u64* glist, const int* gcnt, int lcap, int ny,

@@ -19,19 +19,22 @@ static_assert(sizeof(RangeSeg) == 32 && offsetof(RangeAuxH, seg) == 8192, "Range
 constexpr int64_t kRangePairBytes = 32ll << 20;  // first-pass pair buffer of one block (12 B per pair)
 constexpr int kRangeScanRows = 64;               // rows per workgroup of the scan, at least
 
-struct RangeStats {
-    int64_t total = 0, tier = VS_RANGE_SCAN, rescanned = 0, host_sorted = 0;
-};
+}  // namespace
+
+namespace vs {
 
 bool range_screen_applies(const vs_index* ix, const vs_sel* sel, int nqb) {
     return !sel && (ix->dtype == DT_BF16 || ix->dtype == DT_F16) && nqb > GEMV_NQ_MAX && nqb <= MFMA_QB;
 }
 
-// One block of <= MFMA_QB device queries: counts[q] = the query's result count; unless count_only,
-// its rows are appended to res (D, I, S) in query order, each query's best first.
+// (declared in vs_index.h)  self: the block's queries are stored rows (vs_rows_host.hip); the kernels
+// reject the rows it excludes before they are counted, so everything below sees the filtered answer
 void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int nqb, const float* rad, bool screen,
-                 bool count_only, hipStream_t st, RangeStats& stt, int64_t* counts, vs_range_result* res) {
-    const int64_t nseq = sel ? sel->m : ix->ntotal;
+                 bool count_only, hipStream_t st, RangeStats& stt, int64_t* counts, vs_range_result* res,
+                 const RangeSelf& self) {
+    // (VS_SELF_ABOVE without a selector: no row below row0 can pass, the scan skips them)
+    const int64_t row0 = sel ? 0 : self.row0;
+    const int64_t nseq = sel ? sel->m : ix->ntotal - row0;
     // every query of the block gets an equal region of the first-pass buffer (all of its rows when
     // they fit); a query that finds more is rerun into a region of the size it counted
     const int64_t capq = count_only ? 0 : std::min<int64_t>(nseq, std::max<int64_t>(1, kRangePairBytes / (12 * nqb)));
@@ -64,6 +67,9 @@ void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int n
     a.cap = (const int64_t*)(ad + offsetof(RangeAuxH, cap));
     a.psc = c->rng_p[0].as<double>();
     a.pid = (uint32_t*)(a.psc + capq * nqb);
+    a.self = self.ids;
+    a.self_mode = self.mode;
+    a.row0 = row0;
     auto read_counts = [&] {
         HIP_CHECK(hipMemcpyAsync(h.cnt, a.cnt, sizeof(h.cnt[0]) * nqb, hipMemcpyDeviceToHost, st));
     };
@@ -220,7 +226,7 @@ void range_note_stats(vs_index* ix, const RangeStats& s) {
 }
 
 
-}  // namespace
+}  // namespace vs
 
 void vs::range_search_host(vs_index* ix, const vs_sel* sel, const float* q, int64_t nq, const float* radius,
                            int64_t max_total, vs_range_result* out) {

@@ -1015,6 +1015,41 @@ void scatter_padded(const StagedOut& o, int64_t q0, int64_t m, int k, int kk, fl
     }
 }
 
+void search_staged(vs_index* ix, Ctx* c, int64_t m, int kk, const StagedOut& so, hipStream_t st, bool mirror) {
+    c->outD.ensure((size_t)kk * sizeof(float));
+    c->outI.ensure((size_t)kk * sizeof(int64_t));
+    c->cert.ensure(sizeof(int));
+    const int Kp = screen_depth(kk);
+    const SearchOut one{c->outD.as<float>(), c->outI.as<int64_t>(), nullptr, c->cert.as<int>()};  // a re-searched query
+    search_all(ix, c, c->qdev.as<float>(), m, kk, Kp, SearchOut{so.Dd, so.Id, nullptr, so.cert_d}, st, kOptimisticSeedRank);
+    fetch_staged(c, so, st);
+    // exactness certificate failed for some queries (near-ties deeper than the margin):
+    // re-screen those queries one at a time with a 4x deeper candidate set; past the
+    // deepest screen (more than KP_MAX rows tied within its margin) the exact full scan
+    for (int64_t qi = 0; qi < m; ++qi) {
+        int Kr = Kp;
+        while (!so.cert_h[qi]) {
+            if (Kr < 0) throw VsError(VS_ERR_INTERNAL, "full scan left a query uncertified");
+            if (Kr >= KP_MAX || Kr >= ix->ntotal) {
+                HIP_CHECK(hipMemsetAsync(c->cert.p, 0, sizeof(int), st));
+                full_scan_block(ix, c, c->qdev.as<float>() + qi * ix->d, 1, kk, one, st, ScanOpts());
+                Kr = -1;
+            } else {
+                Kr = (int)std::min<int64_t>(std::min<int64_t>((int64_t)Kr * 4, KP_MAX), round_up(ix->ntotal, 16));
+                search_all(ix, c, c->qdev.as<float>() + qi * ix->d, 1, kk, Kr, one, st, /*safe seed*/ 0);
+            }
+            HIP_CHECK(hipMemcpyAsync(so.Dk + qi * kk, c->outD.p, kk * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(so.Ik + qi * kk, c->outI.p, kk * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipMemcpyAsync(&so.cert_h[qi], c->cert.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            if (mirror) {
+                HIP_CHECK(hipMemcpyAsync(so.Dd + qi * kk, c->outD.p, kk * sizeof(float), hipMemcpyDeviceToDevice, st));
+                HIP_CHECK(hipMemcpyAsync(so.Id + qi * kk, c->outI.p, kk * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+            }
+            HIP_CHECK(hipStreamSynchronize(st));
+        }
+    }
+}
+
 }  // namespace vs
 
 extern "C" {
@@ -1105,39 +1140,11 @@ int vs_search(vs_index* ix, const float* q, int64_t nq, int32_t k, float* D, int
         Ctx* c = L.c;
         hipStream_t st = c->stream;
         const int64_t chunk = stage_chunk(ix, nq, kk, true);
-        c->outD.ensure((size_t)kk * sizeof(float));
-        c->outI.ensure((size_t)kk * sizeof(int64_t));
-        c->cert.ensure(sizeof(int));
-        const int Kp = screen_depth(kk);
-        const SearchOut one{c->outD.as<float>(), c->outI.as<int64_t>(), nullptr, c->cert.as<int>()};  // a re-searched query
         for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
             const int64_t m = std::min(chunk, nq - q0);
             stage_queries(ix, c, q, q0, m, st);
             const StagedOut so = staged_out(c, m, kk, true);
-            search_all(ix, c, c->qdev.as<float>(), m, kk, Kp, SearchOut{so.Dd, so.Id, nullptr, so.cert_d}, st,
-                       kOptimisticSeedRank);
-            fetch_staged(c, so, st);
-            // exactness certificate failed for some queries (near-ties deeper than the margin):
-            // re-screen those queries one at a time with a 4x deeper candidate set; past the
-            // deepest screen (more than KP_MAX rows tied within its margin) the exact full scan
-            for (int64_t qi = 0; qi < m; ++qi) {
-                int Kr = Kp;
-                while (!so.cert_h[qi]) {
-                    if (Kr < 0) throw VsError(VS_ERR_INTERNAL, "full scan left a query uncertified");
-                    if (Kr >= KP_MAX || Kr >= ix->ntotal) {
-                        HIP_CHECK(hipMemsetAsync(c->cert.p, 0, sizeof(int), st));
-                        full_scan_block(ix, c, c->qdev.as<float>() + qi * ix->d, 1, kk, one, st, ScanOpts());
-                        Kr = -1;
-                    } else {
-                        Kr = (int)std::min<int64_t>(std::min<int64_t>((int64_t)Kr * 4, KP_MAX), round_up(ix->ntotal, 16));
-                        search_all(ix, c, c->qdev.as<float>() + qi * ix->d, 1, kk, Kr, one, st, /*safe seed*/ 0);
-                    }
-                    HIP_CHECK(hipMemcpyAsync(so.Dk + qi * kk, c->outD.p, kk * sizeof(float), hipMemcpyDeviceToHost, st));
-                    HIP_CHECK(hipMemcpyAsync(so.Ik + qi * kk, c->outI.p, kk * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-                    HIP_CHECK(hipMemcpyAsync(&so.cert_h[qi], c->cert.p, sizeof(int), hipMemcpyDeviceToHost, st));
-                    HIP_CHECK(hipStreamSynchronize(st));
-                }
-            }
+            search_staged(ix, c, m, kk, so, st, false);
             scatter_padded(so, q0, m, k, kk, fillD, D, I);
         }
     });

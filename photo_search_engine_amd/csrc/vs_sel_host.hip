@@ -41,10 +41,10 @@ namespace {
 // against 7.4 ms on 1M bf16 rows (crossover near 2.2); at 26 the overfetch tier wins 4x and 23x.
 // 3 sits between the two crossovers.  DESIGN §5 "Filtered search".
 constexpr double kSelScanFactor = 3.0;
-struct SelPlan {
-    int tier;  // VS_SEL_SCAN / VS_SEL_OVERFETCH
-    int kp;    // the overfetch depth k' (0 for the scan)
-};
+
+}  // namespace
+
+namespace vs {
 
 SelPlan sel_plan(const vs_index* ix, const vs_sel* sel, int64_t nq, int k) {
     const int kmax = KP_MAX * 4 / 5;
@@ -61,6 +61,10 @@ SelPlan sel_plan(const vs_index* ix, const vs_sel* sel, int64_t nq, int k) {
     return {VS_SEL_OVERFETCH, kp};
 }
 
+}  // namespace vs
+
+namespace {
+
 // k_sel_scan over one query block: full_scan_block's sizing with the list length in place of the
 // row count (rows_per_wg, the scratch budget, <= CUs and <= FS_B workgroups).  Counted nowhere:
 // vs_full_scan_count / vs_uncertified_count speak of the unfiltered screens.
@@ -73,6 +77,10 @@ void sel_scan_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* q, int
     const int qy = std::max(1, std::min(nqb, ix->num_cu / a.G));
     HIP_CHECK(launch_sel_scan(a, sel->ids, sel->m, qy, st));
 }
+
+}  // namespace
+
+namespace vs {
 
 // One batch of device queries through the planned tier; outputs device [nq][k].  Returns the
 // queries the overfetch tier left short and the scan re-answered.  Synchronises st on that tier.
@@ -138,7 +146,7 @@ void sel_note_stats(vs_index* ix, const vs_sel* sel, const SelPlan& plan, int64_
 }
 
 
-}  // namespace
+}  // namespace vs
 
 void vs::search_sel_device(vs_index* ix, const vs_sel* sel, const float* q_dev, int64_t nq, int k, float* D_dev,
                            int64_t* I_dev, double* S64_dev, hipStream_t st) {

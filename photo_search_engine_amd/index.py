@@ -67,6 +67,51 @@ def range_radius(radius, nq: int) -> np.ndarray:
     return np.ascontiguousarray(r)
 
 
+SELF_MODES = {"keep": 0, "drop": 1, "above": 2}
+
+
+def row_ids(ids, ntotal: int) -> np.ndarray:
+    """The ids of a query-from-rows call as a contiguous 1-D int64 array (repeats and any order are
+    fine); anything but 1-D integers raises ``ValueError``.  Ids outside ``[0, ntotal)`` are left to
+    the library, which rejects them before anything is launched."""
+    arr = ids if isinstance(ids, np.ndarray) else np.asarray(list(ids))
+    if arr.size == 0:
+        arr = np.zeros((0,), dtype=np.int64)
+    if arr.ndim != 1 or arr.dtype.kind not in "iu":
+        raise ValueError("ids must be a 1-D sequence of integer row ids")
+    return np.ascontiguousarray(arr, dtype=np.int64)
+
+
+def drop_self_topk(D: np.ndarray, I: np.ndarray, ids: np.ndarray, k: int, metric_type: int):
+    """``vs_search_rows``'s VS_SELF_DROP on the host: from lists ``min(k + 1, ntotal)`` deep, the entry
+    whose id is ``ids[i]`` taken out (else the first ``k`` kept), padded to ``k`` columns."""
+    n, kk = I.shape
+    fill = np.float32(-3.4028235e38 if metric_type == METRIC_IP else 3.4028235e38)
+    Do = np.full((n, k), fill, dtype=np.float32)
+    Io = np.full((n, k), -1, dtype=np.int64)
+    hit = I == ids[:, None]
+    slot = np.where(hit.any(axis=1), hit.argmax(axis=1), kk)
+    src = np.arange(min(k, kk))[None, :] + (np.arange(min(k, kk))[None, :] >= slot[:, None])
+    ok = src < kk
+    srcc = np.minimum(src, kk - 1)
+    Do[:, :src.shape[1]] = np.where(ok, np.take_along_axis(D, srcc, axis=1), fill)
+    Io[:, :src.shape[1]] = np.where(ok, np.take_along_axis(I, srcc, axis=1), -1)
+    return Do, Io
+
+
+def filter_range_self(lims: np.ndarray, D: np.ndarray, I: np.ndarray, ids: np.ndarray, mode: int):
+    """``vs_range_search_rows``'s VS_SELF_DROP / VS_SELF_ABOVE on the host: a range result of the rows
+    ``ids`` as queries without the entries the mode excludes (order kept)."""
+    if mode == SELF_MODES["keep"] or I.shape[0] == 0:
+        return lims, D, I
+    n = lims.shape[0] - 1
+    query = np.repeat(np.arange(n), np.diff(lims))
+    keep = I != ids[query] if mode == SELF_MODES["drop"] else I > ids[query]
+    out = np.zeros((n + 1,), dtype=np.int64)
+    out[1:] = np.cumsum(np.bincount(query[keep], minlength=n))
+    return out, D[keep], I[keep]
+
+
 def _take_range_result(L, h, nq: int):
     """Copy an owned ``vs_range_result`` into numpy arrays (lims, D, I) and free it."""
     try:
@@ -222,6 +267,64 @@ class FlatIndex:
             if own is not None:
                 own.close()
         return _take_range_result(self._L, h, nq)
+
+    def search_rows(self, ids, k: int, sel=None, drop_self: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """:meth:`search` with stored rows as the queries (``vs_search_rows``): query ``i`` is the stored
+        value of row ``ids[i]`` as :meth:`reconstruct` returns it, gathered on the device -- no query
+        crosses the host.  ``drop_self`` (default) leaves row ``ids[i]`` itself out of its own list, by
+        id (an identical row with a lower id comes first and stays): the search runs one entry deeper
+        and the list is padded as :meth:`search` pads it.  ``drop_self=False`` is bit-equal to
+        ``search(reconstruct rows, k, sel)``.  ``ids`` may repeat, in any order; ``sel`` as in
+        :meth:`search`."""
+        ids = row_ids(ids, self.ntotal)
+        n = ids.shape[0]
+        k = int(k)
+        if k <= 0:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "k must be > 0")
+        D = np.empty((n, k), dtype=np.float32)
+        I = np.empty((n, k), dtype=np.int64)
+        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
+        s = own or sel
+        try:
+            if s is not None and s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            check(self._L.vs_search_rows(self._h, s._h if s is not None else None, _ptr(ids), n, k,
+                                         SELF_MODES["drop" if drop_self else "keep"], _ptr(D), _ptr(I)))
+        finally:
+            if own is not None:
+                own.close()
+        return D, I
+
+    def range_search_rows(self, radius, ids=None, sel=None, self_mode: str = "above",
+                          max_total: Optional[int] = None):
+        """:meth:`range_search` with stored rows as the queries (``vs_range_search_rows``): ``ids=None``
+        is the whole-corpus self-join (rows ``0..ntotal-1``); ``radius`` a scalar or one value per
+        query.  ``self_mode``: ``"above"`` returns only rows with an id above the query's own, so a
+        self-join lists every pair once, as (lower id, higher id), and scans only the rows that can
+        still pass; ``"drop"`` leaves out the row itself; ``"keep"`` is bit-equal to
+        ``range_search(reconstruct rows, radius, sel)``.  The excluded rows are never counted:
+        ``max_total`` and :meth:`range_last_stats` see the filtered answer."""
+        if self_mode not in SELF_MODES:
+            raise ValueError(f"unknown self_mode {self_mode!r}")
+        cap = 0 if max_total is None else int(max_total)
+        if max_total is not None and cap <= 0:
+            raise ValueError("max_total must be > 0")
+        ids = None if ids is None else row_ids(ids, self.ntotal)
+        n = self.ntotal if ids is None else ids.shape[0]
+        r = range_radius(radius, n)
+        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
+        s = own or sel
+        h = ctypes.c_void_p()
+        try:
+            if s is not None and s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            check(self._L.vs_range_search_rows(self._h, s._h if s is not None else None,
+                                               _ptr(ids) if ids is not None else None, n, _ptr(r),
+                                               SELF_MODES[self_mode], cap, ctypes.byref(h)))
+        finally:
+            if own is not None:
+                own.close()
+        return _take_range_result(self._L, h, n)
 
     def set_range_mode(self, mode: str) -> None:
         """Force the tier of range searches (``"scan"``, ``"screen"`` where it applies) or let the
@@ -617,6 +720,51 @@ class MultiDeviceFlatIndex:
     def selector(self, allowed) -> MaskSelector:
         """A reusable filter over the rows present now (mask or ids, ``pack_allowed``)."""
         return MaskSelector(self.ntotal, allowed)
+
+    def _rows_as_queries(self, ids: np.ndarray) -> np.ndarray:
+        n = self.ntotal
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+            raise _lib.VsError(_lib.VS_ERR_ARG, f"row ids must lie in [0, ntotal = {n})")
+        q = np.empty((ids.shape[0], self.d), dtype=np.float32)
+        for r0 in range(0, n, 65536):
+            here = np.flatnonzero((ids >= r0) & (ids < r0 + 65536))
+            if here.size:
+                q[here] = self.reconstruct_n(r0, min(65536, n - r0))[ids[here] - r0]
+        return q
+
+    def search_rows(self, ids, k: int, sel=None, drop_self: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """:meth:`FlatIndex.search_rows` over all devices.  This route crosses the host: the rows come
+        back through ``reconstruct_n``, go in again as the queries of :meth:`search` (one entry deeper
+        under ``drop_self``) and the row itself is dropped on the host.  The bits are those of the
+        one-device call, because ``reconstruct_n`` returns the stored values."""
+        ids = row_ids(ids, self.ntotal)
+        k = int(k)
+        if k <= 0:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "k must be > 0")
+        q = self._rows_as_queries(ids)
+        if not drop_self or ids.shape[0] == 0:
+            return self.search(q, k, sel=sel)
+        D, I = self.search(q, min(k + 1, self.ntotal), sel=sel)
+        return drop_self_topk(D, I, ids, k, self.metric_type)
+
+    def range_search_rows(self, radius, ids=None, sel=None, self_mode: str = "above",
+                          max_total: Optional[int] = None):
+        """:meth:`FlatIndex.range_search_rows` over all devices.  This route crosses the host: the rows
+        come back through ``reconstruct_n``, go in again as the queries of :meth:`range_search`, and the
+        drop / above filter runs on the host (so ``max_total`` is checked against the filtered count
+        here, after the unfiltered search).  Bit-equal to the one-device call."""
+        if self_mode not in SELF_MODES:
+            raise ValueError(f"unknown self_mode {self_mode!r}")
+        if max_total is not None and int(max_total) <= 0:
+            raise ValueError("max_total must be > 0")
+        ids = np.arange(self.ntotal, dtype=np.int64) if ids is None else row_ids(ids, self.ntotal)
+        r = range_radius(radius, ids.shape[0])
+        lims, D, I = self.range_search(self._rows_as_queries(ids), r, sel=sel)
+        lims, D, I = filter_range_self(lims, D, I, ids, SELF_MODES[self_mode])
+        if max_total is not None and int(lims[-1]) > int(max_total):
+            raise _lib.VsError(_lib.VS_ERR_ARG,
+                               f"range search found {int(lims[-1])} results, max_total is {int(max_total)}")
+        return lims, D, I
 
     def reconstruct_n(self, i0: int, n: int) -> np.ndarray:
         out = np.empty((int(n), self.d), dtype=np.float32)

@@ -337,6 +337,83 @@ class VectorStore:
         return [{"metadata": self.metadata[index], "distance": float(distance)}
                 for distance, index in zip(distances[:n].tolist(), indices[:n].tolist())]
 
+    def search_similar(self, photo_path: str, top_k: int, allowed=None) -> List[Dict]:
+        """The ``top_k`` items most similar to a photo the store holds, the photo itself left out (an
+        addition at the boundary): :meth:`search`'s result dicts for the stored row of ``photo_path``
+        as the query.  It replaces the reference's ``Searcher.search_by_image_path``
+        (core/searcher.py:1751-1814: the row reconstructed to a Python list, ``max(k + 1, 5 k)``
+        results fetched and the photo's own path filtered out afterwards) with one call in which the
+        query never leaves the device and the photo is removed by its id -- exact under ties: a copy
+        of the photo with a lower id stays and comes first.  ``top_k`` is clamped to ``ntotal - 1``;
+        an empty store returns ``[]``; a path the store does not hold raises ``ValueError``;
+        ``allowed`` as in :meth:`search`.  HNSW stores answer through the exact flat path, as filtered
+        calls do.  One difference from the reference's route: the stored row is the query as it is
+        and is not normalised a second time (the reference sends it through ``search``, which
+        divides the already normalised row by its norm again)."""
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        index = self._path_to_index.get(photo_path)
+        if index is None or index >= self.index.ntotal:
+            raise ValueError(f"未找到图片: {photo_path}")
+        k = min(int(top_k), int(self.index.ntotal) - 1)
+        if k <= 0:
+            return []
+        sel = None if allowed is None else self._allowed_rows(allowed)
+        distances, indices = self.index.search_rows(np.asarray([index], dtype=np.int64), k, sel=sel, drop_self=True)
+        return [{"metadata": self.metadata[i], "distance": float(distance)}
+                for distance, i in zip(distances[0].tolist(), indices[0].tolist()) if i != -1]
+
+    def _allowed_mask(self, allowed) -> np.ndarray:
+        """``allowed`` (a boolean mask, item ids or a predicate over the metadata) as a boolean mask."""
+        n = int(self.index.ntotal)
+        return np.unpackbits(pack_allowed(n, self._allowed_rows(allowed)), bitorder="little")[:n].astype(bool)
+
+    def duplicate_pairs(self, threshold: float, allowed=None, max_pairs: Optional[int] = None):
+        """Every pair of items closer than ``threshold`` -- ``distance`` above it (cosine) or below it
+        (L2), the value :meth:`search` reports -- as arrays ``(i, j, distance)`` with ``i < j``, each
+        pair once, ordered by ``i`` and best first within it.  One self-join on the device
+        (``range_search_rows(..., self_mode="above")``): no row crosses the host, no pair comes twice.
+        ``allowed`` (a boolean mask, item ids or a predicate over the metadata) restricts both sides
+        of a pair; ``max_pairs`` bounds the answer (beyond it the call raises, naming the count)."""
+        empty = (np.empty((0,), dtype=np.int64), np.empty((0,), dtype=np.int64), np.empty((0,), dtype=np.float32))
+        if self.index is None or self.index.ntotal == 0:
+            return empty
+        ids = mask = None
+        if allowed is not None:
+            mask = self._allowed_mask(allowed)
+            ids = np.flatnonzero(mask).astype(np.int64)
+            if ids.shape[0] < 2:
+                return empty
+        lims, distances, indices = self.index.range_search_rows(float(threshold), ids=ids, sel=mask, self_mode="above",
+                                                                max_total=max_pairs)
+        first = np.arange(int(self.index.ntotal), dtype=np.int64) if ids is None else ids
+        return np.repeat(first, np.diff(lims)), indices, distances
+
+    def find_duplicates(self, threshold: float, allowed=None) -> List[List[int]]:
+        """Groups of near-duplicate items: the connected components of :meth:`duplicate_pairs` (a chain
+        a-b, b-c is one group even when a and c are further apart than ``threshold``) as lists of
+        item ids, each ascending, ordered by their first id; items without a duplicate are left out.
+        The union-find runs on the host over the pair list."""
+        first, second, _ = self.duplicate_pairs(threshold, allowed=allowed)
+        parent: Dict[int, int] = {}
+
+        def find(x: int) -> int:
+            root = x
+            while parent.setdefault(root, root) != root:
+                root = parent[root]
+            while parent[x] != root:  # path compression
+                parent[x], x = root, parent[x]
+            return root
+
+        for a, b in zip(first.tolist(), second.tolist()):
+            ra, rb = find(a), find(b)
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)  # (the root is the group's smallest id)
+        groups: Dict[int, List[int]] = {}
+        for x in sorted(parent):
+            groups.setdefault(find(x), []).append(x)
+        return [groups[root] for root in sorted(groups)]
+
     def _allowed_rows(self, allowed):
         """A predicate over the metadata as a boolean mask over the items; selectors, masks and ids pass."""
         if callable(allowed):
