@@ -27,7 +27,9 @@
  *
  * Threading: concurrent vs_search* calls on one handle are safe (shared corpus, one stream +
  * workspace per call from a pool).  vs_add, vs_add_device, vs_add_synthetic, vs_reset and vs_remove_ids
- * take an exclusive lock.
+ * take an exclusive lock.  vs_kmeans takes the shared lock for its whole run, as a search does: it may
+ * run beside searches and other vs_kmeans calls on the handle (each call owns its streams, workspace
+ * and temporary centroid index), while adds, resets and removals wait for it.
  */
 #ifndef VS_H_
 #define VS_H_
@@ -383,6 +385,55 @@ int vs_search_rows(vs_index* index, const vs_sel* sel, const int64_t* ids, int64
 int vs_range_search_rows(vs_index* index, const vs_sel* sel, const int64_t* ids, int64_t n, const float* radius,
                          int32_t self_mode, int64_t max_total, vs_range_result** out);
 
+/* ==== k-means over stored rows ================================================================
+ * "Sort these photos into k visual groups" and "train an IVF's coarse quantizer on what the index
+ * holds": faiss::Clustering / faiss.Kmeans (the family of IndexFlat and IndexIVFFlat, faiss-cpu,
+ * requirements.txt:5) over rows that stay in HBM.  The reference has no such call.
+ *
+ * Members: rows 0..ntotal-1 (m = ntotal), or with a selector its allowed rows (m = vs_sel_count; a
+ * stale selector is VS_ERR_ARG).  A member's point is its stored value exactly as vs_reconstruct
+ * returns it, not normalised again.  metric is the ASSIGNMENT metric (VS_METRIC_IP / VS_METRIC_L2,
+ * -1 = the index's own): unit-norm cosine stores cluster properly under L2.
+ *
+ * Assignment pass t = 0, 1, ...: every member goes to its exact best centroid under the canonical
+ * fp64 score S (oracle/vs_oracle.c), ties to the lower centroid id; the centroids are the fp32 values
+ * as given.  changed[t] = members whose label differs from pass t - 1 (changed[0] = m);
+ * objective[t] = the fp64 sum of the members' S in pass t (summation order unspecified).  A pass
+ * t >= 1 with changed[t] == 0 ends the call (a fixed point), as does pass t == niter; otherwise
+ * update t runs and pass t + 1 follows.  *iters_done = updates run; entries of objective / changed
+ * past the last pass are left untouched.  labels, D and counts describe the last pass, i.e. they are
+ * consistent with the returned centroids.  niter = 0 is "assign the stored rows to these centroids".
+ *
+ * Update (reproducible to the bit): a cluster's members in ascending id are cut into segments of
+ * VS_KMEANS_SEG consecutive members (the last one shorter); a segment's partial starts at +0.0 and
+ * adds its members' values, widened to fp64, one after the other; the cluster's sum starts at +0.0
+ * and adds the partials in segment order; the centroid is (float)(sum / (double)count) per column.
+ * No FMA, no reassociation.  An empty cluster keeps its centroid.  The result is a pure function of
+ * the inputs: it does not depend on the staging size, streams or launch geometry.
+ *
+ * k < 1, k > m, niter < 0, a bad metric, null centroids or null labels are VS_ERR_ARG, checked
+ * before anything is launched (centroids untouched); with m = 0 only k < 1 (and those not about m)
+ * fail: the call writes counts = 0, objective[0] = 0, changed[0] = 0, *iters_done = 0.  The call
+ * takes the shared lock and synchronises.  Its workspace -- the temporary centroid index's search
+ * contexts, the gathered query chunk (vs_set_kmeans_staging_bytes: process-wide, default 256 MiB,
+ * floor one 256-row block: any smaller value, down to 1, means one block; < 1 is VS_ERR_ARG), the
+ * labels, the member order and the partials -- is counted in vs_device_bytes_live and freed before
+ * the call returns. */
+#define VS_KMEANS_SEG 256
+int vs_kmeans(vs_index* index, const vs_sel* sel, int32_t k, int32_t niter, int32_t metric,
+              float* centroids,      /* host k x d fp32: in = initial, out = final */
+              int64_t* labels,       /* host m: cluster of each member, members in ascending id */
+              float* D,              /* host m: (float)S of the member against its centroid; may be NULL */
+              int64_t* counts,       /* host k: members per cluster under `labels`; may be NULL */
+              double* objective,     /* host niter + 1; may be NULL */
+              int64_t* changed,      /* host niter + 1; may be NULL */
+              int32_t* iters_done);  /* updates performed; may be NULL */
+int vs_set_kmeans_staging_bytes(int64_t bytes);
+/* measurement hook (scripts/kmeans_timing.py): the last vs_kmeans call of the process, up to `cap` (5)
+ * values: ms in assignment, in grouping (labels, sort, the host's segment list) and in the update
+ * kernels (HIP events on the call's stream, summed over its passes), passes run, updates run */
+int vs_kmeans_last_times(double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids
@@ -423,7 +474,8 @@ int64_t vs_multi_shard_rows(const vs_multi* m, int shard);
  * Not a reference call site: the reference's VectorStore offers flat and HNSW only
  * (utils/vector_store.py:51-53, 72-81).  This is the faiss IndexIVFFlat surface (faiss-cpu,
  * requirements.txt:5): IndexIVFFlat(quantizer, d, nlist, metric) -> vs_ivf_create,
- * .train -> vs_ivf_set_centroids (k-means runs in the Python layer over vs_ivf_assign),
+ * .train -> vs_ivf_set_centroids (k-means runs in the Python layer over vs_ivf_assign, or on the
+ * device over a flat index's rows: vs_kmeans),
  * .add -> vs_ivf_add, .search with .nprobe -> vs_ivf_search, .reconstruct -> vs_ivf_reconstruct.
  * Semantics (made exact, oracle/ivf_oracle.py): rows go to their exact best centroid (ties ->
  * lower list id) by its stored (dtype-rounded) values; a query probes its exact top-nprobe centroids and gets the exact top-k of the

@@ -118,6 +118,11 @@ _SIGS = {
     # queries taken from stored rows
     "vs_search_rows": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "vs_range_search_rows": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _vp, ctypes.c_int32, _c_i64, ctypes.POINTER(_vp)]),
+    # k-means over stored rows
+    "vs_kmeans": (ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 ctypes.POINTER(ctypes.c_int32)]),
+    "vs_set_kmeans_staging_bytes": (ctypes.c_int, [_c_i64]),
+    "vs_kmeans_last_times": (ctypes.c_int, [_vp, ctypes.c_int]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

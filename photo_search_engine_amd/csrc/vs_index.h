@@ -1,6 +1,6 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
-// vs_api.hip, vs_remove.hip).
+// vs_api.hip, vs_remove.hip, vs_kmeans.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -561,6 +561,29 @@ struct RowsTakeArgs {
 };
 hipError_t launch_rows_take(const RowsTakeArgs& a, int64_t nq, hipStream_t st);
 
+// ---- k-means over stored rows (vs_kmeans.hip) ---------------------------------------
+// mem[i] = sel_ids[i] (null: i) for the m members, ascending
+hipError_t launch_km_members(const uint32_t* sel_ids, int64_t m, int64_t* mem, hipStream_t st);
+// lab[i] = (int)I[i]; *changed += labels that differ from lab's earlier contents, counts[label] += 1
+// (the caller zeroes both first); *bad = 1 if a label lies outside [0, k)
+hipError_t launch_km_labels(const int64_t* I, int64_t m, int k, int32_t* lab, unsigned* counts,
+                            unsigned long long* changed, int* bad, hipStream_t st);
+// part[0, km_obj_blocks(m)) = partial sums of S[0, m) in a fixed order
+int km_obj_blocks(int64_t m);
+hipError_t launch_km_objsum(const double* S, int64_t m, double* part, hipStream_t st);
+// one stable LSD radix pass over bits [shift, shift + 8) of keys_in (vals_in null = positions 0..m-1);
+// table: 256 * km_sort_blocks(m) words of scratch.  No atomic decides a slot.
+int64_t km_sort_blocks(int64_t m);
+hipError_t launch_km_sort_pass(const int32_t* keys_in, const uint32_t* vals_in, int64_t m, int shift, unsigned* table,
+                               int32_t* keys_out, uint32_t* vals_out, hipStream_t st);
+// P[s][0, d) = the fp64 sum, in order, of rows mem[order[seg[s].x + j]], j < seg[s].y <= VS_KMEANS_SEG,
+// read from the tiled layout (one wave per segment and 8 chunk columns); m members, n_valid stored rows
+hipError_t launch_km_segsum(int dt, const uint8_t* data, int d, int dpad, const int64_t* mem, const uint32_t* order,
+                            const uint2* seg, int64_t nseg, int64_t m, int64_t n_valid, double* P, hipStream_t st);
+// cen[c] = (float)((P[segoff[c]] + ... + P[segoff[c + 1] - 1]) / counts[c]); counts[c] == 0: untouched
+hipError_t launch_km_finalize(const double* P, const int64_t* segoff, const unsigned* counts, int k, int d, float* cen,
+                              hipStream_t st);
+
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
 // int8 screen copy of stored rows [r0, r0 + n) (maxes[0..1]: running max ||x_hat||, max beta)
@@ -683,8 +706,10 @@ void range_search_host(vs_index* ix, const vs_sel* sel, const float* q, int64_t 
                        int64_t max_total, vs_range_result* out);
 // S concurrent exact device searches over parts of one batch (own streams and workspaces;
 // unres[i] counts part i's full-scanned queries)
+// D_dev / S64_dev (optional): the fp32 and canonical fp64 scores, [nq][k] like I_dev
 void search_exact_device_parts(vs_index* ix, const float* q_dev, int64_t nq, int k, int64_t* I_dev,
-                               hipStream_t* streams, int S, unsigned* unres);
+                               hipStream_t* streams, int S, unsigned* unres, float* D_dev = nullptr,
+                               double* S64_dev = nullptr);
 // two-phase exact device search (vs_search_device_phase_a / _b)
 bool two_phase_ok(const vs_index* ix, int64_t nq, int k);
 vs_pending* search_phase_a(vs_index* ix, const float* q_dev, int64_t nq, int k, int world, int64_t id_offset,

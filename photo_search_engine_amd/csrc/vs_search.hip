@@ -809,7 +809,7 @@ void vs::search_exact_device(vs_index* ix, const float* q_dev, int64_t nq, int k
 // workspace and serialise on it); a part's full-scanned queries count in unres[part] (if given).  The IVF
 // coarse assignment: one 256-row block of a small quantizer fills only nlist / 256 workgroups.
 void vs::search_exact_device_parts(vs_index* ix, const float* q_dev, int64_t nq, int k, int64_t* I_dev,
-                                   hipStream_t* streams, int S, unsigned* unres) {
+                                   hipStream_t* streams, int S, unsigned* unres, float* D_dev, double* S64_dev) {
     check_index(ix);
     if (nq <= 0) return;
     std::shared_lock<std::shared_mutex> lk(ix->rw);
@@ -823,10 +823,11 @@ void vs::search_exact_device_parts(vs_index* ix, const float* q_dev, int64_t nq,
         const int64_t q0 = std::min(nq, blocks * i / S * MFMA_QB), q1 = std::min(nq, blocks * (i + 1) / S * MFMA_QB);
         if (q1 <= q0) continue;
         Ctx* c = leases[i]->c;
-        c->outD.ensure((size_t)(q1 - q0) * k * sizeof(float));
+        if (!D_dev) c->outD.ensure((size_t)(q1 - q0) * k * sizeof(float));
         c->cert.ensure((size_t)(q1 - q0) * sizeof(int));
         UnresScope us(c, unres ? unres + i : nullptr);  // reset even if search_all throws
-        const SearchOut out{c->outD.as<float>(), I_dev + q0 * k, nullptr, c->cert.as<int>()};
+        const SearchOut out{D_dev ? D_dev + q0 * k : c->outD.as<float>(), I_dev + q0 * k,
+                            S64_dev ? S64_dev + q0 * k : nullptr, c->cert.as<int>()};
         search_all(ix, c, q_dev + q0 * ix->d, q1 - q0, k, Kp, out, streams[i], kOptimisticSeedRank, true);
     }
 }

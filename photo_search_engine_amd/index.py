@@ -133,6 +133,93 @@ def _take_range_result(L, h, nq: int):
         L.vs_range_free(h)
 
 
+KMEANS_METRICS = {"ip": METRIC_IP, "cosine": METRIC_IP, "inner_product": METRIC_IP, "l2": METRIC_L2,
+                  "euclidean": METRIC_L2}
+
+
+class KMeansResult:
+    """What :meth:`FlatIndex.kmeans` returns.  ``centroids`` (k, d) fp32; ``labels`` / ``distances`` (m,):
+    the cluster of each member (members in ascending id) and its fp32 score against that centroid,
+    both from the last assignment pass, so they are consistent with ``centroids``; ``counts`` (k,)
+    members per cluster; ``objective`` / ``changed``: one entry per assignment pass run
+    (``n_iter + 1`` of them); ``n_iter``: centroid updates run."""
+
+    __slots__ = ("centroids", "labels", "distances", "counts", "objective", "changed", "n_iter")
+
+    def __init__(self, centroids, labels, distances, counts, objective, changed, n_iter) -> None:
+        self.centroids = centroids
+        self.labels = labels
+        self.distances = distances
+        self.counts = counts
+        self.objective = objective
+        self.changed = changed
+        self.n_iter = int(n_iter)
+
+
+def kmeans_metric(metric, index_metric_type: int) -> int:
+    """The assignment metric of a k-means call as a code: ``None`` = the index's own; a string as
+    :class:`FlatIndex` takes it; anything else raises ``ValueError``."""
+    if metric is None:
+        return int(index_metric_type)
+    if isinstance(metric, str) and metric.lower() in KMEANS_METRICS:
+        return KMEANS_METRICS[metric.lower()]
+    raise ValueError(f"unknown metric {metric!r}")
+
+
+def kmeans_args(k, niter, members: int):
+    """``(k, niter)`` of a k-means call over ``members`` rows, checked before any library call:
+    ``1 <= k <= members`` and ``niter >= 0``, else ``ValueError``."""
+    k, niter = int(k), int(niter)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if k > int(members):
+        raise ValueError(f"k = {k} exceeds the {int(members)} members")
+    if niter < 0:
+        raise ValueError("niter must be >= 0")
+    return k, niter
+
+
+def kmeans_check_init(init, k: int, d: int) -> None:
+    """The shape of ``init`` (see :func:`kmeans_init`), checked before the members are known."""
+    if init is None:
+        return
+    arr = np.asarray(init)
+    if arr.ndim == 2 and arr.shape == (int(k), int(d)):
+        return
+    if arr.ndim == 1 and arr.shape[0] == int(k) and arr.dtype.kind in "iu":
+        return
+    raise ValueError(f"init must be a ({int(k)}, {int(d)}) array or {int(k)} member ids, got shape {arr.shape}")
+
+
+def kmeans_init(init, k: int, d: int, seed: int, member_ids: np.ndarray, reconstruct) -> np.ndarray:
+    """The (k, d) fp32 initial centroids of a k-means call.  ``init`` is a (k, d) array, ``k`` member
+    ids (integers: their stored rows), or ``None``: ``k`` distinct members drawn with
+    ``np.random.default_rng(seed)`` and sorted (``IVFFlatIndex.train``'s recipe).  Rows are fetched
+    with ``reconstruct(id)``.  A wrong shape or an id that is no member raises ``ValueError``."""
+    if init is None:
+        pick = np.sort(np.random.default_rng(seed).permutation(member_ids.shape[0])[:k])
+        ids = member_ids[pick]
+    else:
+        arr = np.asarray(init)
+        if arr.ndim == 2:
+            if arr.shape != (k, d):
+                raise ValueError(f"init must be a ({k}, {d}) array or {k} member ids, got shape {arr.shape}")
+            return np.ascontiguousarray(arr, dtype=np.float32)
+        if arr.ndim != 1 or arr.shape[0] != k or arr.dtype.kind not in "iu":
+            raise ValueError(f"init must be a ({k}, {d}) array or {k} member ids, got shape {arr.shape}")
+        ids = arr.astype(np.int64)
+        if not np.isin(ids, member_ids).all():
+            raise ValueError("init ids must be members (allowed rows of the index)")
+    return np.ascontiguousarray(np.stack([reconstruct(int(i)) for i in ids]), dtype=np.float32)
+
+
+def kmeans_centroids(centroids, d: int) -> np.ndarray:
+    c = np.ascontiguousarray(centroids, dtype=np.float32)
+    if c.ndim != 2 or c.shape[1] != d or c.shape[0] < 1:
+        raise ValueError(f"centroids must be a (k, {d}) array with k >= 1, got shape {c.shape}")
+    return c
+
+
 class Selector:
     """A set of row ids of one :class:`FlatIndex` (``vs_sel``, include/vs.h): faiss's
     ``IDSelectorBitmap`` uploaded and compacted once, reused across searches.  It covers the rows
@@ -144,6 +231,7 @@ class Selector:
         self._index = index  # (keeps the index alive while the selector is)
         self._L = index._L
         bitmap = np.ascontiguousarray(pack_allowed(index.ntotal, allowed))
+        self._bitmap, self._n = bitmap, index.ntotal  # (the member ids of a k-means call)
         h = ctypes.c_void_p()
         check(self._L.vs_sel_create(index._h, _ptr(bitmap), bitmap.shape[0], ctypes.byref(h)))
         self._h = h
@@ -157,6 +245,7 @@ class Selector:
         self._index = index
         self._L = index._L
         bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8)
+        self._bitmap, self._n = bitmap, index.ntotal
         h = ctypes.c_void_p()
         check(self._L.vs_sel_create(index._h, _ptr(bitmap), bitmap.shape[0], ctypes.byref(h)))
         self._h = h
@@ -325,6 +414,70 @@ class FlatIndex:
             if own is not None:
                 own.close()
         return _take_range_result(self._L, h, n)
+
+    def _kmeans_call(self, s, k: int, niter: int, metric: int, c: np.ndarray, m: int) -> KMeansResult:
+        labels = np.empty((m,), dtype=np.int64)
+        D = np.empty((m,), dtype=np.float32)
+        counts = np.zeros((k,), dtype=np.int64)
+        objective = np.zeros((niter + 1,), dtype=np.float64)
+        changed = np.zeros((niter + 1,), dtype=np.int64)
+        done = ctypes.c_int32(0)
+        check(self._L.vs_kmeans(self._h, s._h if s is not None else None, k, niter, metric, _ptr(c), _ptr(labels),
+                                _ptr(D), _ptr(counts), _ptr(objective), _ptr(changed), ctypes.byref(done)))
+        n = int(done.value)
+        return KMeansResult(c, labels, D, counts, objective[: n + 1].copy(), changed[: n + 1].copy(), n)
+
+    def _members(self, s) -> np.ndarray:
+        """Ascending ids of the members of a k-means call under selector ``s`` (``None``: every row)."""
+        if s is None:
+            return np.arange(self.ntotal, dtype=np.int64)
+        return np.flatnonzero(np.unpackbits(s._bitmap, bitorder="little")[: s._n]).astype(np.int64)
+
+    def kmeans(self, k: int, niter: int = 20, init=None, seed: int = 1234, sel=None, metric=None) -> KMeansResult:
+        """Exact k-means over the stored rows (``vs_kmeans``, include/vs.h): the members -- every row,
+        or the rows ``sel`` allows -- are assigned to their exact best centroid under ``metric``
+        (``"ip"`` / ``"l2"``; ``None`` = the index's own) and the centroids are recomputed on the device
+        in a fixed summation order, so the result is reproducible to the bit.  ``init``: a (k, d)
+        array, ``k`` member ids, or ``None`` for ``k`` distinct members drawn with
+        ``np.random.default_rng(seed)``.  It stops after ``niter`` updates or at a fixed point.
+        Returns a :class:`KMeansResult`."""
+        code = kmeans_metric(metric, self.metric_type)
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        if int(niter) < 0:
+            raise ValueError("niter must be >= 0")
+        kmeans_check_init(init, int(k), self.d)
+        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
+        s = own or sel
+        try:
+            if s is not None and s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            members = self._members(s)
+            k, niter = kmeans_args(k, niter, members.shape[0])
+            c = kmeans_init(init, k, self.d, seed, members, self.reconstruct).copy()
+            return self._kmeans_call(s, k, niter, code, c, members.shape[0])
+        finally:
+            if own is not None:
+                own.close()
+
+    def assign_rows(self, centroids, sel=None, metric=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The ``niter = 0`` form of :meth:`kmeans`: ``(labels, distances)`` of the members against the
+        given centroids -- bit-equal to ``search(reconstruct rows, 1)`` on a flat index of them."""
+        code = kmeans_metric(metric, self.metric_type)
+        c = kmeans_centroids(centroids, self.d).copy()
+        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
+        s = own or sel
+        try:
+            if s is not None and s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            m = self.ntotal if s is None else s.count
+            if c.shape[0] > m:
+                raise ValueError(f"k = {c.shape[0]} exceeds the {m} members")
+            r = self._kmeans_call(s, c.shape[0], 0, code, c, m)
+            return r.labels, r.distances
+        finally:
+            if own is not None:
+                own.close()
 
     def set_range_mode(self, mode: str) -> None:
         """Force the tier of range searches (``"scan"``, ``"screen"`` where it applies) or let the
@@ -607,6 +760,25 @@ def set_remove_staging_bytes(nbytes: int = REMOVE_STAGING_DEFAULT) -> None:
     check(_lib.load().vs_set_remove_staging_bytes(int(nbytes)))
 
 
+KMEANS_STAGING_DEFAULT = 256 << 20
+
+
+def set_kmeans_staging_bytes(nbytes: int = KMEANS_STAGING_DEFAULT) -> None:
+    """Bytes of gathered fp32 queries a ``kmeans`` / ``assign_rows`` call may hold at once, process-wide
+    (include/vs.h ``vs_set_kmeans_staging_bytes``): any value from 1 up, floored at one 256-row block.
+    The results are the same bits under every value."""
+    check(_lib.load().vs_set_kmeans_staging_bytes(int(nbytes)))
+
+
+def kmeans_last_times() -> dict:
+    """The last ``vs_kmeans`` call of the process: ms in assignment, grouping and the update kernels
+    (HIP events, summed over the passes), passes and updates run."""
+    buf = (ctypes.c_double * 5)()
+    check(_lib.load().vs_kmeans_last_times(buf, 5))
+    return {"assign_ms": float(buf[0]), "group_ms": float(buf[1]), "update_ms": float(buf[2]),
+            "passes": int(buf[3]), "updates": int(buf[4])}
+
+
 def synthesize_device(device: int, seed: int, global_row0: int, n: int, d: int, out_ptr: int, normalize: bool = True,
                       dtype: str = "f32", stream: Optional[int] = None) -> None:
     """Write synthetic rows [global_row0, +n) as row-major fp32 (rounded to ``dtype``) to device
@@ -798,6 +970,33 @@ class MultiDeviceFlatIndex:
         if len(nodes) == 0:
             return np.full((0, int(W)), -1, dtype=np.int32)
         return self._one_device_copy().hnsw_prune(nodes, cand, W)
+
+    def kmeans(self, k: int, niter: int = 20, init=None, seed: int = 1234, sel=None, metric=None) -> KMeansResult:
+        """:meth:`FlatIndex.kmeans` on the one-device copy of the rows (a multi-GPU k-means is not
+        offered); ``sel``: a boolean mask, ids or a :class:`MaskSelector`."""
+        kmeans_metric(metric, self.metric_type)
+        if int(k) < 1:
+            raise ValueError("k must be >= 1")
+        if int(niter) < 0:
+            raise ValueError("niter must be >= 0")
+        kmeans_check_init(init, int(k), self.d)
+        return self._one_device_copy().kmeans(k, niter, init, seed, self._copy_sel(sel), metric)
+
+    def assign_rows(self, centroids, sel=None, metric=None) -> Tuple[np.ndarray, np.ndarray]:
+        """:meth:`FlatIndex.assign_rows` on the one-device copy of the rows."""
+        kmeans_metric(metric, self.metric_type)
+        kmeans_centroids(centroids, self.d)
+        return self._one_device_copy().assign_rows(centroids, self._copy_sel(sel), metric)
+
+    def _copy_sel(self, sel):
+        """A filter of this index as one over its one-device copy (rows added after a
+        :class:`MaskSelector` was made are not selected)."""
+        if not isinstance(sel, MaskSelector):
+            return sel
+        mask = np.zeros((self.ntotal,), dtype=bool)
+        n = min(sel.n, mask.shape[0])
+        mask[:n] = np.unpackbits(sel.bitmap, bitorder="little")[:n].astype(bool)
+        return mask
 
     def hnsw_search(self, graph: dict, q: np.ndarray, k: int, ef: int) -> np.ndarray:
         """Ids (nq x k, -1 padded) of faiss's HNSW search over ``graph`` on the one-device copy of

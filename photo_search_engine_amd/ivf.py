@@ -110,6 +110,25 @@ class IVFFlatIndex:
             c[nz] = (sums[nz] / cnt[nz, None]).astype(np.float32)
         self.set_centroids(c)
 
+    def train_from(self, index, niter: int = 10, seed: int = 1234, sel=None) -> None:
+        """Train on rows a flat index already holds (``index.kmeans``, include/vs.h ``vs_kmeans``): the
+        rows stay in HBM, assignment and centroid update both run on the device, and the centroids
+        are reproducible to the bit.  ``index``: a :class:`~.index.FlatIndex` (or anything with its
+        ``kmeans``) of the same dimension; ``sel`` restricts the training rows.  The initial
+        centroids are ``nlist`` distinct rows drawn with ``np.random.default_rng(seed)``, the
+        assignment metric is this index's; empty clusters keep their centroid, as in :meth:`train`."""
+        if int(getattr(index, "d", -1)) != self.d:
+            raise ValueError(f"train_from expects an index of dimension {self.d}, got {getattr(index, 'd', None)}")
+        if int(niter) < 0:
+            raise ValueError("niter must be >= 0")
+        if self.ntotal:
+            raise ValueError("train_from() needs an empty index (reset() first)")
+        if sel is None and int(index.ntotal) < self.nlist:
+            raise ValueError(f"need at least nlist={self.nlist} training rows, got {int(index.ntotal)}")
+        res = index.kmeans(self.nlist, niter=int(niter), seed=seed, sel=sel,
+                           metric="ip" if self.metric_type == METRIC_IP else "l2")
+        self.set_centroids(res.centroids)
+
     def add(self, x) -> None:
         x = self._rows(x, "add")
         check(self._L.vs_ivf_add(self._h, _ptr(x), x.shape[0]))

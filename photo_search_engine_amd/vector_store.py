@@ -414,6 +414,45 @@ class VectorStore:
             groups.setdefault(find(x), []).append(x)
         return [groups[root] for root in sorted(groups)]
 
+    def cluster_items(self, n_clusters: int, allowed=None, niter: int = 20, seed: int = 1234) -> List[Dict]:
+        """The items sorted into ``n_clusters`` visual groups, one cover photo each (an addition at the
+        boundary; faiss's ``Kmeans`` over the rows the index holds): exact k-means on the device
+        (``index.kmeans``) under L2 assignment -- unit-norm cosine rows cluster properly under it --
+        from ``n_clusters`` items drawn with ``np.random.default_rng(seed)``.  Returns one dict per
+        non-empty cluster, ``{"items": [item ids, ascending], "representative": id, "size": n}``,
+        largest first (ties: the lower cluster id); ``representative`` is the item closest to its
+        cluster's centroid (ties: the lower id).  ``allowed`` (a boolean mask, item ids or a predicate
+        over the metadata) restricts the items; fewer allowed items than ``n_clusters`` clamp the
+        cluster count; an empty store, or nothing allowed, gives ``[]``.  The result is reproducible
+        to the bit."""
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        if int(n_clusters) < 1:
+            raise ValueError("n_clusters must be >= 1")
+        if allowed is None:
+            mask = None
+            members = np.arange(int(self.index.ntotal), dtype=np.int64)
+        else:
+            mask = self._allowed_mask(allowed)
+            members = np.flatnonzero(mask).astype(np.int64)
+        if members.shape[0] == 0:
+            return []
+        k = min(int(n_clusters), int(members.shape[0]))
+        res = self.index.kmeans(k, niter=int(niter), seed=seed, sel=mask, metric="l2")
+        labels = np.asarray(res.labels)
+        dist = np.asarray(res.distances)
+        clusters = []
+        for c in range(k):
+            pos = np.flatnonzero(labels == c)
+            if pos.shape[0] == 0:
+                continue
+            best = pos[np.argmin(dist[pos])]  # (argmin: the first of equal distances, the lower id)
+            clusters.append((-int(pos.shape[0]), c, {"items": members[pos].tolist(),
+                                                     "representative": int(members[best]),
+                                                     "size": int(pos.shape[0])}))
+        clusters.sort(key=lambda t: (t[0], t[1]))
+        return [t[2] for t in clusters]
+
     def _allowed_rows(self, allowed):
         """A predicate over the metadata as a boolean mask over the items; selectors, masks and ids pass."""
         if callable(allowed):
