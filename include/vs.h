@@ -434,6 +434,60 @@ int vs_set_kmeans_staging_bytes(int64_t bytes);
  * kernels (HIP events on the call's stream, summed over its passes), passes run, updates run */
 int vs_kmeans_last_times(double* out, int cap);
 
+/* ==== diversified search ======================================================================
+ * "The best k results, one per group of look-alikes": cameras shoot bursts, and a library that holds
+ * twelve frames of one moment answers a query with ten frames of the same wave.  The reference's
+ * _deduplicate_results (core/searcher.py:242) merges equal paths only, and its relaxation and expansion
+ * rounds (core/searcher.py:1157-1211, :1352-1458) re-search with a larger candidate_k to fill the page
+ * back up.  vs_search_diverse answers each query q with a suppression radius r_q (fp32, one per query)
+ * exactly, on the device, at any depth.
+ *
+ * Members: every stored row (sel NULL), or the rows the selector allows; a stale selector is
+ * VS_ERR_ARG and rows added after the selector was made are not members (the rules of vs_search_sel).
+ * Ranking: the members in vs_search's total order for q -- canonical fp64 score S, then the lower id.
+ * Near: rows a and b are near iff (float)S(a, b) passes r_q strictly (inner product D > r, L2 D < r),
+ * S(a, b) the canonical score of the two stored values as vs_reconstruct returns them.  This is the
+ * predicate of vs_range_search_rows: b is near a exactly when that call with ids = {a}, radius = r
+ * returns b.  The relation is symmetric bit for bit and NOT transitive, so the order of the walk is
+ * part of the contract:
+ * Walk: go through the ranking best first; a row is accepted iff it is near no row accepted before
+ * it, otherwise it is hidden under the earliest-accepted row it is near; the walk ends with the k-th
+ * acceptance or with the ranking.
+ *
+ * Outputs (host): D, I (nq x k) the accepted rows in acceptance order, D the value vs_search reports
+ * for the row, unfilled slots -1 / -+FLT_MAX; hidden (int32 nq x k, may be NULL) the rows hidden under
+ * each accepted row among the rows examined, unfilled slots 0; examined (int64 nq, may be NULL) the
+ * rows of the ranking the walk looked at: the rank of the k-th accepted row plus one, or the member
+ * count when the ranking ran out.  sum(hidden[q]) + accepted[q] == examined[q].
+ *
+ * r = +inf (inner product) / -inf (L2): nothing is near, the result is bit-equal to vs_search /
+ * vs_search_sel.  r = -inf / +inf: everything is near, only the top row is returned and examined is the
+ * member count.  A NaN radius, k <= 0, k beyond vs_search's limit (3276) and null q / radius / D / I
+ * are VS_ERR_ARG, checked before anything is launched; nq = 0 returns at once; an empty index or a
+ * selector that allows nothing gives all padding and examined = 0.  The walk holds a stored row in
+ * LDS as an fp64 query: d > 14336 is VS_ERR_ARG.  Shared lock, one leased context, the call
+ * synchronises (the shape of vs_search_rows).
+ *
+ * The accepted list is prefix-stable -- walking deeper only appends -- so a walk over the first L rows
+ * of the ranking yields an exact prefix of the answer.  Every query is exact; the list lengths below
+ * change the work, never the bits: (1) the exact top-L0 of every query, L0 = min(first, members),
+ * walked on the device; (2) queries with fewer than k accepted rows whose list was shorter than the
+ * member set are re-searched at 4 L, up to min(limit, members), and walked again; (3) a query still
+ * short gets its whole ranking (the range-search scan with an infinite radius), walked by the same
+ * kernel -- thousands of identical embeddings at the top of a ranking are still answered.  Tier 3's
+ * lists are counted in vs_device_bytes_live and freed before the call returns. */
+int vs_search_diverse(vs_index* index, const vs_sel* sel, const float* q, int64_t nq, int32_t k,
+                      const float* radius, float* D, int64_t* I, int32_t* hidden, int64_t* examined);
+/* list lengths the walk is fed (tests; results are the same bits under every setting):
+ * first = 0 -> max(4 k, 64), limit = 0 -> vs_search's k limit; 1 <= first <= limit <= that limit */
+int vs_set_diverse_depth(vs_index* index, int32_t first, int32_t limit);
+/* last call on the handle, up to cap (5): {queries, complete after the first list, complete after a
+ * deeper list, answered from the full ranking, longest list walked} */
+int vs_diverse_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/diverse_timing.py): the last call on the handle, up to cap (6): ms of
+ * HIP-event time {list search, walk} of tier 1, of tier 2 and of tier 3 ({ranking, walk}) */
+int vs_diverse_last_times(vs_index* index, double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

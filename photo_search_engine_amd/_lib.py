@@ -123,6 +123,11 @@ _SIGS = {
                                  ctypes.POINTER(ctypes.c_int32)]),
     "vs_set_kmeans_staging_bytes": (ctypes.c_int, [_c_i64]),
     "vs_kmeans_last_times": (ctypes.c_int, [_vp, ctypes.c_int]),
+    # diversified search
+    "vs_search_diverse": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "vs_set_diverse_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
+    "vs_diverse_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_diverse_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

@@ -1,6 +1,6 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
-// vs_api.hip, vs_remove.hip, vs_kmeans.hip).
+// vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,6 +46,7 @@ struct Ctx {
     DevBuf rng_D, rng_I, rng_S;  // ... the block's emitted results
     DevBuf row_ids;           // queries taken from stored rows: the call's ids, uploaded once
     DevBuf row_out;           // ... a chunk's lists without the rows themselves ([I int64 | D fp32], k_rows_take)
+    DevBuf dv_out;            // diversified search: the walk's radii and outputs
     DevBuf rsc, rdone;        // split refine: per-query scores + ids of the kept rows, done counters
     DevBuf pa;       // two-phase (sharded) search: the refine's phase-1 state between the launches
     DevBuf rows[2];  // read_rows_host: unpacked fp32 chunks
@@ -120,6 +121,13 @@ struct vs_index {
     std::atomic<int> range_mode{VS_RANGE_AUTO};
     std::mutex range_mu;
     int64_t range_stats[4] = {0, 0, 0, 0};
+    // diversified search: the list lengths set by vs_set_diverse_depth (0 = the defaults); the last
+    // call's {queries, complete after the first list, after a deeper list, answered from the full
+    // ranking, longest list walked} (vs_diverse_last_stats)
+    std::atomic<int> dv_first{0}, dv_limit{0};
+    std::mutex dv_mu;
+    int64_t dv_stats[5] = {0, 0, 0, 0, 0};
+    double dv_times[6] = {0, 0, 0, 0, 0, 0};  // ... and its HIP-event ms {search, walk} per tier (vs_diverse_last_times)
     int last_kernel_kind = 0;  // 1 = mfma, 2 = gemv, 3 = int8 mfma, 4 = int8 gemv, 5 = exact full scan
     // Screen health (first passes of MFMA batches): the certificate-failure count of a batch is read
     // back without a host wait (pinned word + event, observed by a later search).  A failed query

@@ -584,6 +584,31 @@ hipError_t launch_km_segsum(int dt, const uint8_t* data, int d, int dpad, const 
 hipError_t launch_km_finalize(const double* P, const int64_t* segoff, const unsigned* counts, int k, int d, float* cen,
                               hipStream_t st);
 
+// ---- diversified search (vs_diverse.hip) ---------------------------------------------
+constexpr int DV_THREADS = 256;           // k_diverse_walk: one workgroup per query
+constexpr int DV_BLOCK = 64;              // candidates resolved per step of the walk
+constexpr int DV_K_MAX = KP_MAX * 4 / 5;  // accepted rows kept in LDS (vs_search's k limit)
+struct DiverseArgs {
+    const uint8_t* corpus;  // tiled shard
+    int d, dpad, dt, metric;
+    int64_t n_valid;
+    const int64_t* I_in;    // [nq][L] each query's exact ranking, best first (an entry < 0 ends it)
+    const float* D_in;      // [nq][L] the scores vs_search reports for them
+    int64_t L;              // list length: any
+    const float* radius;    // [nq]
+    int k;                  // <= DV_K_MAX
+    int nqs;                // LDS query slots of a workgroup: diverse_query_slots(d), >= 1
+    int64_t* I;            // [nq][k] accepted rows in acceptance order, -1 padded
+    float* D;               // [nq][k] their D_in, padded with the worst score
+    int32_t* hidden;        // [nq][k] rows hidden under each, 0 padded
+    int32_t* nacc;          // [nq] accepted rows
+    int64_t* examined;      // [nq] list entries the walk looked at
+};
+// candidate rows a workgroup stages at a time as fp64 queries (one per wave, as many of the four as
+// fit in LDS beside the accepted set); 0: d is too large for the walk (d > 14336)
+int diverse_query_slots(int d);
+hipError_t launch_diverse_walk(const DiverseArgs& a, int nq, hipStream_t st);
+
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
 // int8 screen copy of stored rows [r0, r0 + n) (maxes[0..1]: running max ||x_hat||, max beta)

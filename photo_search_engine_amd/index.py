@@ -156,6 +156,24 @@ class KMeansResult:
         self.n_iter = int(n_iter)
 
 
+class DiverseResult:
+    """What :meth:`FlatIndex.search_diverse` returns.  ``D`` / ``I`` (nq, k): the accepted rows in
+    acceptance order, padded with the worst score / ``-1``; ``hidden`` (nq, k) int32: the rows hidden
+    under each accepted row among the rows examined; ``examined`` (nq,) int64: the rows of the ranking
+    the walk looked at.  ``hidden[q].sum() + (I[q] >= 0).sum() == examined[q]``."""
+
+    __slots__ = ("D", "I", "hidden", "examined")
+
+    def __init__(self, D, I, hidden, examined) -> None:
+        self.D = D
+        self.I = I
+        self.hidden = hidden
+        self.examined = examined
+
+    def __iter__(self):
+        return iter((self.D, self.I, self.hidden, self.examined))
+
+
 def kmeans_metric(metric, index_metric_type: int) -> int:
     """The assignment metric of a k-means call as a code: ``None`` = the index's own; a string as
     :class:`FlatIndex` takes it; anything else raises ``ValueError``."""
@@ -478,6 +496,59 @@ class FlatIndex:
         finally:
             if own is not None:
                 own.close()
+
+    def search_diverse(self, q, k: int, radius, sel=None) -> DiverseResult:
+        """Exact top-``k`` with near-duplicates collapsed (``vs_search_diverse``, include/vs.h): the
+        exact ranking of each query is walked best first and a row is accepted iff its fp32 score with
+        every row accepted before it does not pass ``radius`` (``D > radius`` inner product, ``D <
+        radius`` squared L2 -- the predicate of :meth:`range_search_rows`; a scalar or one value per
+        query); otherwise it counts as hidden under the earliest-accepted row it is near.  ``sel`` as
+        in :meth:`search`.  Returns a :class:`DiverseResult`."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search_diverse expects an (nq, {self.d}) array, got {q.shape}")
+        nq = q.shape[0]
+        k = int(k)
+        if k <= 0:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "k must be > 0")
+        r = range_radius(radius, nq)
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        hidden = np.zeros((nq, k), dtype=np.int32)
+        examined = np.zeros((nq,), dtype=np.int64)
+        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
+        s = own or sel
+        try:
+            if s is not None and s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            check(self._L.vs_search_diverse(self._h, s._h if s is not None else None, _ptr(q), nq, k, _ptr(r), _ptr(D),
+                                            _ptr(I), _ptr(hidden), _ptr(examined)))
+        finally:
+            if own is not None:
+                own.close()
+        return DiverseResult(D, I, hidden, examined)
+
+    def set_diverse_depth(self, first: int = 0, limit: int = 0) -> None:
+        """The list lengths :meth:`search_diverse` walks: the first list and the longest one before
+        the full ranking (``0`` = the defaults; the same bits under every setting,
+        ``vs_set_diverse_depth``)."""
+        check(self._L.vs_set_diverse_depth(self._h, int(first), int(limit)))
+
+    def diverse_last_stats(self) -> dict:
+        """The last :meth:`search_diverse`: queries, how many were complete after the first list, after
+        a deeper list, how many were answered from the full ranking, and the longest list walked
+        (``vs_diverse_last_stats``)."""
+        buf = (ctypes.c_int64 * 5)()
+        check(self._L.vs_diverse_last_stats(self._h, buf, 5))
+        return {"queries": int(buf[0]), "first": int(buf[1]), "deeper": int(buf[2]), "full": int(buf[3]),
+                "longest": int(buf[4])}
+
+    def diverse_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`search_diverse`, per tier (``vs_diverse_last_times``)."""
+        buf = (ctypes.c_double * 6)()
+        check(self._L.vs_diverse_last_times(self._h, buf, 6))
+        return {"search_ms": [float(buf[0]), float(buf[2]), float(buf[4])],
+                "walk_ms": [float(buf[1]), float(buf[3]), float(buf[5])]}
 
     def set_range_mode(self, mode: str) -> None:
         """Force the tier of range searches (``"scan"``, ``"screen"`` where it applies) or let the
@@ -987,6 +1058,11 @@ class MultiDeviceFlatIndex:
         kmeans_metric(metric, self.metric_type)
         kmeans_centroids(centroids, self.d)
         return self._one_device_copy().assign_rows(centroids, self._copy_sel(sel), metric)
+
+    def search_diverse(self, q, k: int, radius, sel=None) -> DiverseResult:
+        """:meth:`FlatIndex.search_diverse` on the one-device copy of the rows (a multi-GPU walk is not
+        offered); ``sel``: a boolean mask, ids or a :class:`MaskSelector`."""
+        return self._one_device_copy().search_diverse(q, k, radius, self._copy_sel(sel))
 
     def _copy_sel(self, sel):
         """A filter of this index as one over its one-device copy (rows added after a

@@ -314,6 +314,28 @@ class VectorStore:
             results.append({"metadata": self.metadata[index], "distance": float(distance)})
         return results
 
+    def search_diverse(self, query_embedding: List[float], top_k: int, threshold: float, allowed=None) -> List[Dict]:
+        """:meth:`search` with look-alikes collapsed (an addition at the boundary): the best ``top_k``
+        items, one per group of near-duplicates, each with the number of look-alikes it stands for --
+        ``{"metadata", "distance", "similar_hidden": n}``.  The exact ranking is walked best first; an
+        item is returned iff it is closer than ``threshold`` (:meth:`duplicate_pairs`' meaning: above
+        it for cosine, below it for L2) to no item returned before it, otherwise it is counted under
+        the earliest such item.  A burst of twelve frames then fills one slot, not ten, and the page
+        needs none of the reference's refill rounds (core/searcher.py:242 merges equal paths only;
+        :1157-1211 and :1352-1458 re-search with a larger ``candidate_k``).  The guards, the
+        normalisation and the ``k = min(top_k, ntotal)`` clamp are :meth:`search`'s; ``allowed`` as
+        there.  HNSW stores answer through the exact flat path, as filtered calls do."""
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        if len(query_embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
+        k = min(top_k, self.index.ntotal)
+        sel = None if allowed is None else self._allowed_rows(allowed)
+        res = self.index.search_diverse(self._normalize_query(query_embedding), k, float(threshold), sel=sel)
+        return [{"metadata": self.metadata[index], "distance": float(distance), "similar_hidden": int(hidden)}
+                for distance, index, hidden in zip(res.D[0].tolist(), res.I[0].tolist(), res.hidden[0].tolist())
+                if index != -1]
+
     def search_range(self, query_embedding: List[float], radius: float, allowed=None,
                      max_results: Optional[int] = None) -> List[Dict]:
         """Every item within a score radius, best first (an addition at the boundary; faiss's
