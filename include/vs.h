@@ -488,6 +488,76 @@ int vs_diverse_last_stats(vs_index* index, int64_t* out, int cap);
  * HIP-event time {list search, walk} of tier 1, of tier 2 and of tier 3 ({ranking, walk}) */
 int vs_diverse_last_times(vs_index* index, double* out, int cap);
 
+/* ==== grouped search ==========================================================================
+ * "The best k days for this query, 3 photos of each": rows that belong together by a key -- a shooting
+ * day, a folder, an event, a person, a file hash -- collapsed into one result.  The reference merges
+ * equal paths after over-fetching candidate_k rows (_deduplicate_results, core/searcher.py:242) and
+ * re-searches to fill the page back up (:1157-1211, :1352-1458); Milvus group_by_field, Qdrant
+ * search_groups and Elasticsearch collapse + inner_hits are this call, faiss has none.
+ *
+ * Group keys.  vs_groups_create takes n host int64 keys, one per row; n must equal vs_ntotal
+ * (VS_ERR_ARG otherwise; keys may be NULL when n = 0).  Rows with the same non-negative key form a
+ * group; a row with a negative key is a group of its own (an ungrouped photo).  Rows added after
+ * creation belong to no group and are no members of a grouped search (the selector's n_sel rule); after
+ * vs_reset, or a vs_remove_ids that removed a row, the object is stale (using it is VS_ERR_ARG, the
+ * generation check of vs_sel).  Creation sorts the keys on the host and uploads once -- per row a dense
+ * group index in ascending key order, per group its key and size, per ungrouped row its key -- and the
+ * object is reused across searches.  Shared lock; its HBM is counted in vs_device_bytes_live until
+ * vs_groups_destroy.  vs_groups_count: distinct non-negative keys; vs_groups_rows: rows covered. */
+typedef struct vs_groups vs_groups;
+int vs_groups_create(vs_index* index, const int64_t* keys, int64_t n, vs_groups** out);
+void vs_groups_destroy(vs_groups* groups);
+int64_t vs_groups_count(const vs_groups* groups);
+int64_t vs_groups_rows(const vs_groups* groups);
+/* Members: the rows the groups object covers, with a selector (may be NULL) those of them it allows;
+ * the rules of vs_search_sel hold (a stale selector is VS_ERR_ARG, rows added later are not selected).
+ * Ranking: the members in vs_search's total order for q -- canonical fp64 score S, then the lower id.
+ * Answer: the groups ordered by their best member (first appearance in the ranking), the first k of
+ * them, and of each its best group_size (g) members in ranking order.
+ *
+ * Outputs (host): keys_out (int64 nq x k) the group's key, for an ungrouped row its negative key as
+ * given; D, I (nq x k x g) the members, D = (float)S exactly as vs_search reports it; found (int32
+ * nq x k, may be NULL) the members returned for the group, min(g, members of the group); sizes (int64
+ * nq x k, may be NULL) the members of the group under the selector (1 for an ungrouped row).  A group
+ * slot past the last group has found 0, sizes 0, keys_out INT64_MIN and every I / D entry padded as
+ * vs_search pads (-1 / -+FLT_MAX); member slots past found are padded the same way.
+ *
+ * With all keys negative, or all distinct, and g = 1, I[:, :, 0] and D[:, :, 0] are bit-equal to
+ * vs_search / vs_search_sel at the same k; with all keys equal the one group holds the first g entries
+ * of vs_search(q, g).
+ *
+ * k < 1, group_size < 1, k * group_size beyond vs_search's k limit (3276) or beyond the depth limit
+ * below, null q / keys_out / D / I, groups of another index and stale groups are VS_ERR_ARG, checked
+ * before anything is launched; nq = 0 returns at once; an empty member set gives all padding.  Shared
+ * lock, one leased context, the call synchronises (the shape of vs_search_diverse).
+ *
+ * No query ranks its whole member set.  target = min(k, groups with a member); a walk over a list that
+ * is a prefix of the ranking identifies groups in their true order, so it is complete once it holds
+ * target groups with min(g, members of the group) rows each, or once the list holds every member.
+ * (1) the exact top-L0 of every query, L0 = min(first, limit, members), walked on the device; (2) the
+ * queries not complete re-searched at 4 L up to min(limit, members) and walked again; (3) restricted
+ * rounds, one query at a time: the member set is cut down on the device to the rows that can still
+ * matter -- the rows of identified groups that are short of members and, while fewer than target groups
+ * are identified, the rows of groups not yet seen -- the filtered search's own road ranks the first
+ * min(limit, rows left) of them, the walk runs again and the host merges (an identified group's new
+ * list extends its old one; new groups follow in their order of appearance).  Every round completes or
+ * identifies at least one group because k * group_size <= limit.  The depths change the work, never
+ * the bits.  The rounds' scratch is counted in vs_device_bytes_live and freed before the call returns. */
+int vs_search_groups(vs_index* index, const vs_groups* groups, const vs_sel* sel, const float* q, int64_t nq,
+                     int32_t k, int32_t group_size, int64_t* keys_out, float* D, int64_t* I, int32_t* found,
+                     int64_t* sizes);
+/* list lengths the walk is fed (tests; the same bits under every setting): first = 0 -> max(4 k g, 64),
+ * limit = 0 -> vs_search's k limit; 1 <= first <= limit <= that limit */
+int vs_set_group_depth(vs_index* index, int32_t first, int32_t limit);
+/* last call on the handle, up to cap (6): {queries, complete after the first list, complete after a
+ * deeper list, finished by restricted rounds, restricted rounds run in total, longest list walked} */
+int vs_group_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/groups_timing.py): the last call on the handle, up to cap (8): ms of
+ * HIP-event time {list search, walk} of tier 1, of tier 2 and of the restricted rounds (their list
+ * search = building the restricted set, its compaction and the scan), then the parts of that last
+ * search spent building the restricted set and compacting it */
+int vs_group_last_times(vs_index* index, double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

@@ -128,6 +128,16 @@ _SIGS = {
     "vs_set_diverse_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
     "vs_diverse_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_diverse_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    # grouped search
+    "vs_groups_create": (ctypes.c_int, [_vp, _vp, _c_i64, ctypes.POINTER(_vp)]),
+    "vs_groups_destroy": (None, [_vp]),
+    "vs_groups_count": (_c_i64, [_vp]),
+    "vs_groups_rows": (_c_i64, [_vp]),
+    "vs_search_groups": (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp,
+                                        _vp]),
+    "vs_set_group_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
+    "vs_group_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_group_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

@@ -1,6 +1,6 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
-// vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip).
+// vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,6 +47,7 @@ struct Ctx {
     DevBuf row_ids;           // queries taken from stored rows: the call's ids, uploaded once
     DevBuf row_out;           // ... a chunk's lists without the rows themselves ([I int64 | D fp32], k_rows_take)
     DevBuf dv_out;            // diversified search: the walk's radii and outputs
+    DevBuf gr_out;            // grouped search: the walk's outputs
     DevBuf rsc, rdone;        // split refine: per-query scores + ids of the kept rows, done counters
     DevBuf pa;       // two-phase (sharded) search: the refine's phase-1 state between the launches
     DevBuf rows[2];  // read_rows_host: unpacked fp32 chunks
@@ -128,6 +129,14 @@ struct vs_index {
     std::mutex dv_mu;
     int64_t dv_stats[5] = {0, 0, 0, 0, 0};
     double dv_times[6] = {0, 0, 0, 0, 0, 0};  // ... and its HIP-event ms {search, walk} per tier (vs_diverse_last_times)
+    // grouped search: the list lengths set by vs_set_group_depth (0 = the defaults); the last call's
+    // {queries, complete after the first list, after a deeper list, finished by restricted rounds,
+    // restricted rounds run, longest list walked} (vs_group_last_stats) and its HIP-event ms
+    // (vs_group_last_times)
+    std::atomic<int> gr_first{0}, gr_limit{0};
+    std::mutex gr_mu;
+    int64_t gr_stats[6] = {0, 0, 0, 0, 0, 0};
+    double gr_times[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int last_kernel_kind = 0;  // 1 = mfma, 2 = gemv, 3 = int8 mfma, 4 = int8 gemv, 5 = exact full scan
     // Screen health (first passes of MFMA batches): the certificate-failure count of a batch is read
     // back without a host wait (pinned word + event, observed by a later search).  A failed query
@@ -159,6 +168,18 @@ struct vs_sel {
     int64_t n_sel = 0, m = 0;  // rows covered, rows allowed
     uint64_t* bits = nullptr;  // device: ceil(n_sel / 64) words (zero past the uploaded bytes)
     uint32_t* ids = nullptr;   // device: the m allowed ids, ascending
+};
+
+// ---- group keys: exact grouped search (include/vs.h "grouped search"; kernels: vs_group.hip) ----
+struct vs_groups {
+    vs_index* ix = nullptr;
+    uint64_t gen = 0;  // the index's reset generation at creation
+    int device = 0;
+    int64_t n_cov = 0, G = 0, U = 0;  // rows covered, distinct non-negative keys, ungrouped rows
+    vs::DevBuf gid;    // int32 [n_cov] group codes (vs_internal.h)
+    vs::DevBuf gkey;   // int64 [G] keys, ascending
+    vs::DevBuf gsize;  // int32 [G] rows per group
+    vs::DevBuf ukey;   // int64 [U] keys of the ungrouped rows, in row order
 };
 
 namespace vs {

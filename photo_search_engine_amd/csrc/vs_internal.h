@@ -609,6 +609,48 @@ struct DiverseArgs {
 int diverse_query_slots(int d);
 hipError_t launch_diverse_walk(const DiverseArgs& a, int nq, hipStream_t st);
 
+// ---- grouped search (vs_group.hip) ---------------------------------------------------
+// A row's group code (vs_groups, gid[row]): >= 0 the dense index of its key among the distinct
+// non-negative keys, ascending; < 0 an ungrouped row, ~code its index among the ungrouped keys.
+constexpr int GR_THREADS = 64;            // k_group_walk: one wave per query
+constexpr int GR_BLOCK = 64;              // candidates loaded per step of the walk
+constexpr int GR_K_MAX = KP_MAX * 4 / 5;  // group slots kept in LDS (vs_search's k limit)
+constexpr int GR_TABLE = 8192;            // open-address table of identified groups (>= 2.5 GR_K_MAX)
+constexpr int GR_NONE = -0x7FFFFFFF - 1;  // slot_code of an unused slot
+struct GroupWalkArgs {
+    const int32_t* gid;     // [n_cov] group codes
+    int64_t n_cov;          // rows the groups object covers (list entries at or past it are passed over)
+    const int64_t* gkey;    // [G] keys of the groups
+    const int32_t* gsize;   // [G] members of each group (the object's own sizes, or k_group_count's)
+    const int64_t* ukey;    // [U] keys of the ungrouped rows
+    int metric;
+    const int64_t* I_in;    // [nq][L] each query's exact ranking, best first (an entry < 0 ends it)
+    const float* D_in;      // [nq][L] the scores vs_search reports for them
+    int64_t L;              // list length: any
+    int k, g;               // group slots and member slots per group of the outputs: k * g <= GR_K_MAX
+    int k_target;           // groups a walk accepts: 1 .. k
+    int64_t* keys;          // [nq][k] group keys in order of first appearance, INT64_MIN padded
+    int64_t* I;             // [nq][k][g] members in list order, -1 padded
+    float* D;               // [nq][k][g] their D_in, padded with the worst score
+    int32_t* found;         // [nq][k] members held, 0 padded
+    int32_t* sizes;         // [nq][k] gsize of the group (1 for an ungrouped row), 0 padded
+    int32_t* slot_code;     // [nq][k] the group code of each slot, GR_NONE padded
+    int32_t* nacc;          // [nq] groups accepted
+    int32_t* complete;      // [nq] 1 = k_target groups accepted and each holds min(g, gsize) members
+};
+hipError_t launch_group_walk(const GroupWalkArgs& a, int nq, hipStream_t st);
+// gsize[code] += 1 per listed id below n_cov with a group, cnt[0] += groups that got their first member
+// and ungrouped rows listed, cnt[1] += ids below n_cov (gsize [G] and cnt [2] zeroed by the caller)
+hipError_t launch_group_count(const int32_t* gid, int64_t n_cov, const uint32_t* ids, int64_t m, int32_t* gsize,
+                              unsigned* cnt, hipStream_t st);
+// bits[w] (ceil(n_cov / 64) words) = the rows of [0, n_cov) that sel_bits allows (null: every row; rows at
+// or past n_sel are not allowed) and whose group's state byte is 1, or 0 while `open`; ungrouped rows
+// pass while `open`
+hipError_t launch_group_restrict(const int32_t* gid, int64_t n_cov, const uint64_t* sel_bits, int64_t n_sel,
+                                 const uint8_t* state, int open, uint64_t* bits, hipStream_t st);
+// clears the bits of rows ids[0, n) (each < n_cov)
+hipError_t launch_group_clear(uint64_t* bits, int64_t n_cov, const int64_t* ids, int n, hipStream_t st);
+
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
 // int8 screen copy of stored rows [r0, r0 + n) (maxes[0..1]: running max ||x_hat||, max beta)

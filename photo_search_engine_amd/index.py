@@ -286,6 +286,94 @@ class Selector:
             pass
 
 
+GROUP_KG_MAX = 3276  # k * group_size of a grouped search: ``vs_search``'s k limit
+KEY_PAD = np.iinfo(np.int64).min  # ``keys`` of a group slot past the last group
+
+
+class GroupedResult:
+    """What :meth:`FlatIndex.search_groups` returns.  ``keys`` (nq, k) int64: the groups in order of
+    their best member (an ungrouped row's negative key as given; ``KEY_PAD`` past the last group);
+    ``D`` / ``I`` (nq, k, g): each group's best members in ranking order, padded with the worst score /
+    ``-1``; ``found`` (nq, k) int32: the members returned for the group; ``sizes`` (nq, k) int64: the
+    members the group has under the selector."""
+
+    __slots__ = ("keys", "D", "I", "found", "sizes")
+
+    def __init__(self, keys, D, I, found, sizes) -> None:
+        self.keys = keys
+        self.D = D
+        self.I = I
+        self.found = found
+        self.sizes = sizes
+
+    def __iter__(self):
+        return iter((self.keys, self.D, self.I, self.found, self.sizes))
+
+
+def group_key_array(keys, n: int) -> np.ndarray:
+    """The keys of a grouped search as a contiguous int64 array of ``n`` values (one per row); anything
+    but ``n`` integers raises ``ValueError``."""
+    arr = keys if isinstance(keys, np.ndarray) else np.asarray(list(keys))
+    if arr.size == 0:
+        arr = np.zeros((0,), dtype=np.int64)
+    if arr.ndim != 1 or arr.dtype.kind not in "iu" or arr.shape[0] != int(n):
+        raise ValueError(f"group keys must be {int(n)} integers (one per row), got shape {arr.shape} {arr.dtype}")
+    if arr.dtype.kind == "u" and arr.size and int(arr.max()) > np.iinfo(np.int64).max:
+        raise ValueError("group keys must fit int64")
+    return np.ascontiguousarray(arr, dtype=np.int64)
+
+
+def group_args(k, group_size):
+    """``(k, group_size)`` of a grouped search, checked before any library call: both ``>= 1`` and
+    ``k * group_size <= GROUP_KG_MAX``, else ``ValueError``."""
+    k, g = int(k), int(group_size)
+    if k < 1:
+        raise ValueError("k must be >= 1")
+    if g < 1:
+        raise ValueError("group_size must be >= 1")
+    if k * g > GROUP_KG_MAX:
+        raise ValueError(f"k * group_size = {k * g} exceeds {GROUP_KG_MAX}")
+    return k, g
+
+
+class Groups:
+    """The group keys of one :class:`FlatIndex` (``vs_groups``, include/vs.h): one int64 key per row,
+    uploaded once and reused across searches.  Rows with the same non-negative key form a group, a row
+    with a negative key is a group of its own.  It covers the rows present when it was made (rows added
+    later belong to no group and are no members of a grouped search) and is stale after ``reset()`` or a
+    ``remove_ids`` that removed a row."""
+
+    def __init__(self, index: "FlatIndex", keys) -> None:
+        self._h = None
+        self._index = index  # (keeps the index alive while the groups are)
+        self._L = index._L
+        arr = group_key_array(keys, index.ntotal)
+        h = ctypes.c_void_p()
+        check(self._L.vs_groups_create(index._h, _ptr(arr) if arr.size else None, arr.shape[0], ctypes.byref(h)))
+        self._h = h
+
+    @property
+    def count(self) -> int:
+        """Distinct non-negative keys."""
+        return int(self._L.vs_groups_count(self._h))
+
+    @property
+    def rows(self) -> int:
+        """Rows covered."""
+        return int(self._L.vs_groups_rows(self._h))
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            self._L.vs_groups_destroy(self._h)
+        self._h = None
+
+    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FlatIndex:
     """Exact flat inner-product / squared-L2 index resident in one GPU's HBM."""
 
@@ -550,6 +638,69 @@ class FlatIndex:
         return {"search_ms": [float(buf[0]), float(buf[2]), float(buf[4])],
                 "walk_ms": [float(buf[1]), float(buf[3]), float(buf[5])]}
 
+    def group_keys(self, keys) -> Groups:
+        """Reusable :class:`Groups` over the rows present now: ``ntotal`` integer keys, one per row."""
+        return Groups(self, keys)
+
+    def search_groups(self, q, k: int, groups: Groups, group_size: int = 1, sel=None) -> GroupedResult:
+        """Exact top-``k`` groups by key with the best ``group_size`` rows of each
+        (``vs_search_groups``, include/vs.h): the members -- the rows ``groups`` covers, under ``sel``
+        those of them it allows -- are ranked as :meth:`search` ranks them, the groups are ordered by
+        their best member and each comes with its best members in ranking order.  ``sel`` as in
+        :meth:`search`.  Returns a :class:`GroupedResult`."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search_groups expects an (nq, {self.d}) array, got {q.shape}")
+        if not isinstance(groups, Groups):
+            raise TypeError("groups must be a Groups object (FlatIndex.group_keys)")
+        nq = q.shape[0]
+        k, g = int(k), int(group_size)
+        if k < 1 or g < 1:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "k and group_size must be >= 1")
+        keys = np.empty((nq, k), dtype=np.int64)
+        D = np.empty((nq, k, g), dtype=np.float32)
+        I = np.empty((nq, k, g), dtype=np.int64)
+        found = np.zeros((nq, k), dtype=np.int32)
+        sizes = np.zeros((nq, k), dtype=np.int64)
+        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
+        s = own or sel
+        try:
+            if s is not None and s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            if groups._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "groups are closed")
+            check(self._L.vs_search_groups(self._h, groups._h, s._h if s is not None else None, _ptr(q), nq, k, g,
+                                           _ptr(keys), _ptr(D), _ptr(I), _ptr(found), _ptr(sizes)))
+        finally:
+            if own is not None:
+                own.close()
+        return GroupedResult(keys, D, I, found, sizes)
+
+    def set_group_depth(self, first: int = 0, limit: int = 0) -> None:
+        """The list lengths :meth:`search_groups` walks: the first list and the longest one, which the
+        restricted rounds use too (``0`` = the defaults; the same bits under every setting,
+        ``vs_set_group_depth``).  A call with ``k * group_size > limit`` is an argument error."""
+        check(self._L.vs_set_group_depth(self._h, int(first), int(limit)))
+
+    def group_last_stats(self) -> dict:
+        """The last :meth:`search_groups`: queries, how many were complete after the first list, after
+        a deeper list, how many were finished by restricted rounds, the rounds run in total and the
+        longest list walked (``vs_group_last_stats``)."""
+        buf = (ctypes.c_int64 * 6)()
+        check(self._L.vs_group_last_stats(self._h, buf, 6))
+        return {"queries": int(buf[0]), "first": int(buf[1]), "deeper": int(buf[2]), "finished": int(buf[3]),
+                "rounds": int(buf[4]), "longest": int(buf[5])}
+
+    def group_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`search_groups`, per tier, and the parts of the
+        restricted rounds' list search spent building and compacting the restricted set
+        (``vs_group_last_times``)."""
+        buf = (ctypes.c_double * 8)()
+        check(self._L.vs_group_last_times(self._h, buf, 8))
+        return {"search_ms": [float(buf[0]), float(buf[2]), float(buf[4])],
+                "walk_ms": [float(buf[1]), float(buf[3]), float(buf[5])],
+                "restrict_ms": float(buf[6]), "compact_ms": float(buf[7])}
+
     def set_range_mode(self, mode: str) -> None:
         """Force the tier of range searches (``"scan"``, ``"screen"`` where it applies) or let the
         library choose (``"auto"``); the same bits under every mode (``vs_set_range_mode``)."""
@@ -800,6 +951,39 @@ class MaskSelector:
 
     def close(self) -> None:
         pass
+
+
+class HostGroups:
+    """:meth:`MultiDeviceFlatIndex.group_keys`: the group keys of the rows present when it was made,
+    kept on the host (the device object is built on the one-device copy, per state of that copy)."""
+
+    def __init__(self, n: int, keys) -> None:
+        self.n = int(n)
+        self.keys = group_key_array(keys, self.n)
+        self._dev = None  # (the copy it was built on, its row count, Groups)
+
+    @property
+    def count(self) -> int:
+        return int(np.unique(self.keys[self.keys >= 0]).shape[0])
+
+    @property
+    def rows(self) -> int:
+        return self.n
+
+    def on(self, copy: "FlatIndex") -> Groups:
+        """The device groups on ``copy``; rows behind the covered ones get a key of their own (the
+        caller's selector keeps them out of the member set)."""
+        n = copy.ntotal
+        if self._dev is None or self._dev[0] is not copy or self._dev[1] != n or self._dev[2]._h is None:
+            self.close()
+            keys = self.keys if n == self.n else np.concatenate([self.keys, np.full((n - self.n,), -1, dtype=np.int64)])
+            self._dev = (copy, n, Groups(copy, keys))
+        return self._dev[2]
+
+    def close(self) -> None:
+        dev, self._dev = self._dev, None
+        if dev is not None:
+            dev[2].close()
 
 
 def merge_shards_device(metric_type: int, S_ptr: int, I_ptr: int, G: int, nq: int, k: int, S_out: int, I_out: int,
@@ -1063,6 +1247,28 @@ class MultiDeviceFlatIndex:
         """:meth:`FlatIndex.search_diverse` on the one-device copy of the rows (a multi-GPU walk is not
         offered); ``sel``: a boolean mask, ids or a :class:`MaskSelector`."""
         return self._one_device_copy().search_diverse(q, k, radius, self._copy_sel(sel))
+
+    def group_keys(self, keys) -> HostGroups:
+        """Reusable group keys over the rows present now (:meth:`FlatIndex.group_keys`)."""
+        return HostGroups(self.ntotal, keys)
+
+    def search_groups(self, q, k: int, groups: HostGroups, group_size: int = 1, sel=None) -> GroupedResult:
+        """:meth:`FlatIndex.search_groups` on the one-device copy of the rows (a multi-GPU walk is not
+        offered); ``sel``: a boolean mask, ids or a :class:`MaskSelector`."""
+        if not isinstance(groups, HostGroups):
+            raise TypeError("groups must come from this index's group_keys")
+        n = self.ntotal
+        if groups.n > n:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "stale groups (rows were removed after they were made)")
+        copy = self._one_device_copy()
+        s = self._copy_sel(sel)
+        if groups.n < n:  # rows added behind the groups are no members
+            mask = np.zeros((n,), dtype=bool)
+            mask[:groups.n] = True
+            if s is not None:
+                mask &= np.unpackbits(pack_allowed(n, s), bitorder="little")[:n].astype(bool)
+            s = mask
+        return copy.search_groups(q, k, groups.on(copy), group_size, s)
 
     def _copy_sel(self, sel):
         """A filter of this index as one over its one-device copy (rows added after a

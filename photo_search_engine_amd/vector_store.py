@@ -161,6 +161,8 @@ class VectorStore:
         # a flat-configured store loaded from an HNSW file: the reference's index object stays an
         # IndexHNSWFlat (utils/vector_store.py:249), so its save() writes an HNSW file again
         self._file_hnsw = False
+        # search_grouped: the index's group keys object of the field last grouped by, until the items change
+        self._group_cache: Dict[str, Any] = {}
 
     # ------------------------------------------------------------------ internals
     def _rebuild_path_index(self) -> None:
@@ -274,6 +276,7 @@ class VectorStore:
 
         normalized = self._normalize_vector(embedding)
         vector = np.array([normalized], dtype="float32")
+        self._drop_group_cache()
         self.index.add(vector)
         self.metadata.append(metadata)
         self._embeddings[len(self.metadata) - 1] = normalized
@@ -335,6 +338,93 @@ class VectorStore:
         return [{"metadata": self.metadata[index], "distance": float(distance), "similar_hidden": int(hidden)}
                 for distance, index, hidden in zip(res.D[0].tolist(), res.I[0].tolist(), res.hidden[0].tolist())
                 if index != -1]
+
+    def search_grouped(self, query_embedding: List[float], top_k: int, group_by, group_size: int = 1,
+                       allowed=None) -> List[Dict]:
+        """:meth:`search` with the items that belong together by a key collapsed (an addition at the
+        boundary; Milvus ``group_by_field``, Qdrant ``search_groups``, Elasticsearch ``collapse`` with
+        ``inner_hits``): the best ``top_k`` groups -- one per shooting day, folder, event, person or file
+        hash -- ordered by their best item, each with its best ``group_size`` items, as
+        ``{"group": value, "size": n, "items": [{"metadata", "distance"}, ...]}``; ``size`` is the number
+        of items the group has (under ``allowed``), for a "12 photos from this day" label.  The answer
+        is exact at any depth and needs none of the reference's over-fetching and refill rounds
+        (core/searcher.py:242 merges equal paths after fetching ``candidate_k`` rows; :1157-1211 and
+        :1352-1458 re-search to fill the page back up).
+
+        ``group_by``: a metadata field name (an item without the field, or with ``None`` in it, is
+        ungrouped: a group of its own, reported with ``"group": None``); a callable ``metadata ->
+        hashable | None``; or a sequence of one int per item (negative = ungrouped).  Values are coded
+        to int64 in order of first appearance; the device copy of a field's keys is cached until the
+        items change.  The guards, the normalisation and the ``k = min(top_k, ntotal)`` clamp are
+        :meth:`search`'s; ``allowed`` as there; ``k * group_size`` beyond 3276 (the index's depth
+        limit) raises ``ValueError``.  HNSW stores answer through the exact flat path, as filtered
+        calls do."""
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        if len(query_embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
+        n = int(self.index.ntotal)
+        k, g = min(int(top_k), n), int(group_size)
+        if k < 1 or g < 1:
+            raise ValueError("top_k and group_size must be >= 1")
+        if k * g > 3276:
+            raise ValueError(f"top_k * group_size = {k * g} exceeds 3276")
+        groups, values, own = self._group_keys(group_by, n)
+        try:
+            sel = None if allowed is None else self._allowed_rows(allowed)
+            res = self.index.search_groups(self._normalize_query(query_embedding), k, groups, group_size=g, sel=sel)
+        finally:
+            if own:
+                groups.close()
+        out: List[Dict] = []
+        for slot in range(k):
+            found = int(res.found[0, slot])
+            if found == 0:
+                break
+            key = int(res.keys[0, slot])
+            items = [{"metadata": self.metadata[index], "distance": float(distance)}
+                     for distance, index in zip(res.D[0, slot, :found].tolist(), res.I[0, slot, :found].tolist())]
+            out.append({"group": (key if values is None else values[key]) if key >= 0 else None, "size": int(res.sizes[0, slot]), "items": items})
+        return out
+
+    def _group_keys(self, group_by, n: int):
+        """``(groups, values, own)`` of a ``group_by``: the index's group keys object, the value each
+        non-negative key stands for (``None``: the key itself), and whether the caller closes the object (a cached one stays)."""
+        if isinstance(group_by, str):
+            hit = self._group_cache.get(group_by)
+            if hit is not None and hit[0] is self.index and hit[1] == n:
+                return hit[2], hit[3], False
+            raw = [m.get(group_by) if isinstance(m, dict) else None for m in self.metadata[:n]]
+        elif callable(group_by):
+            raw = [group_by(m) for m in self.metadata[:n]]
+        else:
+            keys = np.asarray(group_by)
+            if keys.ndim != 1 or keys.shape[0] != n or keys.dtype.kind not in "iu":
+                raise ValueError(f"group_by must be a field name, a callable or {n} ints (one per item)")
+            return self.index.group_keys(keys.astype(np.int64)), None, True
+        codes: Dict[Any, int] = {}
+        values: List[Any] = []
+        keys = np.empty((n,), dtype=np.int64)
+        for i, value in enumerate(raw):
+            if value is None:
+                keys[i] = -1
+                continue
+            code = codes.get(value)
+            if code is None:
+                code = codes[value] = len(values)
+                values.append(value)
+            keys[i] = code
+        groups = self.index.group_keys(keys)
+        if isinstance(group_by, str):
+            self._drop_group_cache()  # (one field at a time: a page groups by one key)
+            self._group_cache[group_by] = (self.index, n, groups, values)
+            return groups, values, False
+        return groups, values, True
+
+    def _drop_group_cache(self) -> None:
+        cache, self._group_cache = self._group_cache, {}
+        for _, _, groups, _ in cache.values():
+            groups.close()
 
     def search_range(self, query_embedding: List[float], radius: float, allowed=None,
                      max_results: Optional[int] = None) -> List[Dict]:
@@ -566,6 +656,7 @@ class VectorStore:
         if loaded.ntotal:  # payload streamed file -> pinned chunks -> HBM (no host copy of the matrix)
             index.add_from_file(self.index_path, loaded.payload_offset, loaded.ntotal)
         self._drop_graph()
+        self._drop_group_cache()
         self.index = index
         self._persisted = (self._file_state(loaded.ntotal, loaded.d, loaded.metric_type)
                            if loaded.kind == "flat" else None)
@@ -599,6 +690,7 @@ class VectorStore:
     def clear(self) -> None:
         """清空索引与元数据."""
         self._drop_graph()
+        self._drop_group_cache()
         self._file_hnsw = False
         self.index = self._create_index(self.dimension) if self.dimension else None
         self.metadata = []
@@ -787,6 +879,7 @@ class VectorStore:
             self.index = self._create_index(self.dimension)
         if rows.shape[1] != self.dimension:
             raise ValueError(f"向量维度不匹配: {rows.shape[1]} != {self.dimension}")
+        self._drop_group_cache()
         self.index.add(self._normalize_rows(rows))
         base = len(self.metadata)
         self.metadata.extend(metadatas)
@@ -810,6 +903,7 @@ class VectorStore:
         remove = np.unpackbits(pack_allowed(n, ids), bitorder="little")[:n].astype(bool)  # (validates ids / mask)
         if not remove.any():
             return 0
+        self._drop_group_cache()
         removed = int(self.index.remove_ids(remove))
         new_id = np.cumsum(~remove) - 1  # surviving item i -> its new id
         self.metadata = [m for m, gone in zip(self.metadata, remove.tolist()) if not gone]
