@@ -4,9 +4,9 @@
 // A walk over a list that is a prefix of a query's exact ranking identifies groups in their true order
 // (every row not in the list ranks below every row in it), so it is complete once it holds `target`
 // groups with min(g, members of the group) rows each, or once the list held every member.  Tiers:
-//   1  the exact top-L0 of every query (search_staged with the device block mirrored, or
-//      sel_search_ctx), walked on the device;
+//   1  the exact top-L0 of every query (exact_lists, valid on the device), walked on the device;
 //   2  the queries not complete re-searched at 4 L, up to the limit, and walked again from scratch;
+//      (tiers 1 and 2 are deepen_lists of vs_walk.h, shared with the diversified search)
 //   3  restricted rounds, one query at a time: the member set cut down on the device to the rows of the
 //      identified groups still short of members and -- while fewer than `target` groups are identified
 //      -- of the groups not yet seen, compacted into a temporary selector, ranked by the filtered
@@ -16,7 +16,7 @@
 // appear behind every identified one, in true order.  A list that does not hold its whole set holds
 // limit >= k g rows: a row of a group not yet seen identifies that group; otherwise they are rows of at
 // most k short groups, one of which then has g of them and completes.
-#include "vs_index.h"
+#include "vs_walk.h"
 
 using namespace vs;
 
@@ -24,9 +24,7 @@ namespace {
 
 constexpr int64_t kKeyPad = -0x7FFFFFFFFFFFFFFFll - 1;  // INT64_MIN: the key of an unused group slot
 
-struct GrTimes {
-    double search[3] = {0, 0, 0}, walk[3] = {0, 0, 0}, restrict_ms = 0, compact_ms = 0;  // ms (HIP events)
-};
+enum { T_RESTRICT = 6, T_COMPACT = 7 };  // the restricted rounds' own slots of WalkTimes::ms
 
 // the member sets a call works on: the selector the lists are searched under (null: every stored row),
 // the members of each group and the number of groups that have one
@@ -76,21 +74,31 @@ struct GrOut {
     std::vector<int32_t> nacc, complete;      // [nq]
 };
 
-// one walk's results on the host, [m][k'] slots of g entries
-struct GrWalk {
-    std::vector<uint8_t> h;
-    const int64_t *keys, *I;
-    const float* D;
-    const int32_t *found, *sizes, *code, *nacc, *complete;
+// a walk's block for m queries with kk slots of g entries, on the device and copied to the host:
+// [keys int64 mk | I int64 mkg | D fp32 mkg | found, sizes, code int32 mk | nacc, complete int32 m]
+struct GrBlock {
+    int64_t *keys, *I;
+    float* D;
+    int32_t *found, *sizes, *code, *nacc, *complete;
+    size_t bytes;
 };
+GrBlock gr_block(const void* base, size_t m, size_t mk, size_t mkg) {
+    Carver c(base);  // (a braced list is evaluated left to right: the order of the members)
+    GrBlock b{c.take<int64_t>(mk), c.take<int64_t>(mkg), c.take<float>(mkg), c.take<int32_t>(mk), c.take<int32_t>(mk),
+              c.take<int32_t>(mk), c.take<int32_t>(m), c.take<int32_t>(m)};
+    b.bytes = c.used;
+    return b;
+}
 
-// the walk over m device lists [m][L] with kk slots of g entries and k_target groups to accept
-void walk_lists(const vs_index* ix, Ctx* c, const vs_groups* gr, const int32_t* gsize, const int64_t* Id, const float* Dd,
-                int64_t L, int64_t m, int kk, int g, int k_target, GrWalk& w, hipStream_t st, DevEvent* ev_done) {
+// the walk over m device lists [m][L] with kk slots of g entries and k_target groups to accept; returns
+// its results on the host, in h
+GrBlock walk_lists(const vs_index* ix, Ctx* c, const vs_groups* gr, const int32_t* gsize, const int64_t* Id,
+                   const float* Dd, int64_t L, int64_t m, int kk, int g, int k_target, std::vector<uint8_t>& h,
+                   hipStream_t st, DevEvent* ev_done) {
     const size_t mk = (size_t)m * kk, mkg = mk * g;
-    // [keys int64 mk | I int64 mkg | D fp32 mkg | found, sizes, code int32 mk | nacc, complete int32 m]
-    const size_t bytes = mk * 8 + mkg * 8 + mkg * 4 + 3 * mk * 4 + 2 * (size_t)m * 4;
+    const size_t bytes = gr_block(nullptr, m, mk, mkg).bytes;
     c->gr_out.ensure(bytes);
+    const GrBlock dev = gr_block(c->gr_out.p, m, mk, mkg);
     GroupWalkArgs a{};
     a.gid = gr->gid.as<int32_t>();
     a.n_cov = gr->n_cov;
@@ -102,45 +110,30 @@ void walk_lists(const vs_index* ix, Ctx* c, const vs_groups* gr, const int32_t* 
     a.k = kk;
     a.g = g;
     a.k_target = k_target;
-    int64_t* keys_d = c->gr_out.as<int64_t>();
-    int64_t* I_d = keys_d + mk;
-    float* D_d = (float*)(I_d + mkg);
-    int32_t* found_d = (int32_t*)(D_d + mkg);
-    int32_t* sizes_d = found_d + mk;
-    int32_t* code_d = sizes_d + mk;
-    int32_t* nacc_d = code_d + mk;
-    int32_t* comp_d = nacc_d + m;
     const int64_t qmax = 65536;  // workgroups of one launch
     for (int64_t q0 = 0; q0 < m; q0 += qmax) {
         const int nq = (int)std::min(qmax, m - q0);
         a.I_in = Id + q0 * L;
         a.D_in = Dd + q0 * L;
-        a.keys = keys_d + q0 * kk;
-        a.I = I_d + q0 * kk * g;
-        a.D = D_d + q0 * kk * g;
-        a.found = found_d + q0 * kk;
-        a.sizes = sizes_d + q0 * kk;
-        a.slot_code = code_d + q0 * kk;
-        a.nacc = nacc_d + q0;
-        a.complete = comp_d + q0;
+        a.keys = dev.keys + q0 * kk;
+        a.I = dev.I + q0 * kk * g;
+        a.D = dev.D + q0 * kk * g;
+        a.found = dev.found + q0 * kk;
+        a.sizes = dev.sizes + q0 * kk;
+        a.slot_code = dev.code + q0 * kk;
+        a.nacc = dev.nacc + q0;
+        a.complete = dev.complete + q0;
         HIP_CHECK(launch_group_walk(a, nq, st));
     }
     if (ev_done) HIP_CHECK(hipEventRecord(*ev_done, st));
-    w.h.resize(bytes);
-    HIP_CHECK(hipMemcpyAsync(w.h.data(), c->gr_out.p, bytes, hipMemcpyDeviceToHost, st));
+    h.resize(bytes);
+    HIP_CHECK(hipMemcpyAsync(h.data(), c->gr_out.p, bytes, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    w.keys = (const int64_t*)w.h.data();
-    w.I = w.keys + mk;
-    w.D = (const float*)(w.I + mkg);
-    w.found = (const int32_t*)(w.D + mkg);
-    w.sizes = w.found + mk;
-    w.code = w.sizes + mk;
-    w.nacc = w.code + mk;
-    w.complete = w.nacc + m;
+    return gr_block(h.data(), m, mk, mkg);
 }
 
 // a tier-1/2 walk's m answers into rows idx[j] of the call's outputs (every slot is written)
-void deliver_walk(const GrWalk& w, int64_t m, const int64_t* idx, GrOut& out) {
+void deliver_walk(const GrBlock& w, int64_t m, const int64_t* idx, GrOut& out) {
     const int k = out.k;
     const int64_t kg = (int64_t)k * out.g;
     for (int64_t j = 0; j < m; ++j) {
@@ -154,23 +147,6 @@ void deliver_walk(const GrWalk& w, int64_t m, const int64_t* idx, GrOut& out) {
         out.nacc[(size_t)r] = w.nacc[j];
         out.complete[(size_t)r] = w.complete[j];
     }
-}
-
-double ms_between(const DevEvent& a, const DevEvent& b) {
-    float ms = 0.0f;
-    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-    return (double)ms;
-}
-
-void note_stats(vs_index* ix, const int64_t (&s)[6], const GrTimes& t) {
-    std::lock_guard<std::mutex> g(ix->gr_mu);
-    for (int i = 0; i < 6; ++i) ix->gr_stats[i] = s[i];
-    for (int i = 0; i < 3; ++i) {
-        ix->gr_times[2 * i] = t.search[i];
-        ix->gr_times[2 * i + 1] = t.walk[i];
-    }
-    ix->gr_times[6] = t.restrict_ms;
-    ix->gr_times[7] = t.compact_ms;
 }
 
 void check_groups(const vs_index* ix, const vs_groups* gr) {
@@ -198,7 +174,7 @@ struct Round3 {
 };
 
 // returns the rounds run
-int64_t restricted_rounds(Round3& r, const float* q, int64_t qi, GrOut& out, GrTimes& times, int64_t& longest) {
+int64_t restricted_rounds(Round3& r, const float* q, int64_t qi, GrOut& out, WalkTimes& times, int64_t& longest) {
     vs_index* ix = r.ix;
     const vs_groups* gr = r.gr;
     const int k = out.k, g = out.g;
@@ -214,7 +190,7 @@ int64_t restricted_rounds(Round3& r, const float* q, int64_t qi, GrOut& out, GrT
     r.R.bits.ensure((size_t)nwords * 8);
     r.state_h.resize((size_t)std::max<int64_t>(gr->G, 1));
     r.state_d.ensure(r.state_h.size());
-    GrWalk w;
+    std::vector<uint8_t> h;
     std::vector<int> inc;  // the slots of the identified groups still short of members
     int64_t rounds = 0;
     for (;;) {
@@ -254,15 +230,13 @@ int64_t restricted_rounds(Round3& r, const float* q, int64_t qi, GrOut& out, GrT
         const int kk = (int)std::min<int64_t>(r.limit, nR);
         const int kprime = (int)inc.size() + (r.target - identified);
         stage_queries(ix, r.c, q, qi, 1, r.st);
-        const StagedOut so = staged_out(r.c, 1, kk, false);
-        const SelPlan plan = sel_plan(ix, &r.R.s, 1, kk);
-        sel_search_ctx(ix, r.c, &r.R.s, plan, r.c->qdev.as<float>(), 1, kk, SearchOut{so.Dd, so.Id}, r.st);
+        const StagedOut so = exact_lists(ix, r.c, &r.R.s, sel_plan(ix, &r.R.s, 1, kk), 1, kk, LISTS_DEVICE, r.st);
         HIP_CHECK(hipEventRecord(r.e3, r.st));
-        walk_lists(ix, r.c, gr, r.mb.gsize, so.Id, so.Dd, kk, 1, kprime, g, kprime, w, r.st, &r.e4);
-        times.restrict_ms += ms_between(r.e0, r.e1);
-        times.compact_ms += ms_between(r.e1, r.e2);
-        times.search[2] += ms_between(r.e0, r.e3);
-        times.walk[2] += ms_between(r.e3, r.e4);
+        const GrBlock w = walk_lists(ix, r.c, gr, r.mb.gsize, so.Id, so.Dd, kk, 1, kprime, g, kprime, h, r.st, &r.e4);
+        times.ms[T_RESTRICT] += ms_between(r.e0, r.e1);
+        times.ms[T_COMPACT] += ms_between(r.e1, r.e2);
+        times.search(2) += ms_between(r.e0, r.e3);
+        times.walk(2) += ms_between(r.e3, r.e4);
         longest = std::max<int64_t>(longest, kk);
         // merge: an identified group takes the new member list (the old one is its prefix); new groups
         // follow in their order of appearance
@@ -380,7 +354,7 @@ int vs_search_groups(vs_index* ix, const vs_groups* gr, const vs_sel* sel, const
                      int32_t group_size, int64_t* keys_out, float* D, int64_t* I, int32_t* found_out, int64_t* sizes_out) {
     return guarded([&] {
         check_index(ix);
-        const int kmax = KP_MAX * 4 / 5;
+        const int kmax = K_MAX;
         const int g = group_size;
         if (nq < 0) throw VsError(VS_ERR_ARG, "nq must be >= 0");
         if (k < 1) throw VsError(VS_ERR_ARG, "k must be >= 1");
@@ -389,19 +363,20 @@ int vs_search_groups(vs_index* ix, const vs_groups* gr, const vs_sel* sel, const
         std::shared_lock<std::shared_mutex> lk(ix->rw);
         check_groups(ix, gr);
         if (sel) check_sel(ix, sel);
-        const int set_first = ix->gr_first.load(), set_limit = ix->gr_limit.load();
-        const int64_t limit = set_limit > 0 ? set_limit : kmax;
-        if ((int64_t)k * g > limit)
+        const int64_t kg = (int64_t)k * g;
+        const WalkState::Depth depth = ix->gr.resolve(std::max<int64_t>(4 * kg, 64), kmax);
+        const int64_t limit = depth.limit;
+        if (kg > limit)
             throw VsError(VS_ERR_ARG, "k * group_size must be <= the depth limit (vs_set_group_depth): every restricted "
                                       "round needs a list of k * group_size rows to make progress");
         int64_t stats[6] = {nq, 0, 0, 0, 0, 0};
-        GrTimes times;
+        WalkTimes times;
+        auto note = [&] { ix->gr.note(stats, 6, times.ms, 8); };
         if (nq == 0) {
-            note_stats(ix, stats, times);
+            note();
             return;
         }
         if (!q || !keys_out || !D || !I) throw VsError(VS_ERR_ARG, "null host buffer");
-        const int64_t kg = (int64_t)k * g;
         fill_padding(D, I, nq * kg, worst_score(ix));
         std::fill(keys_out, keys_out + nq * k, kKeyPad);
         GrOut out{k, g, keys_out, D, I, std::vector<int32_t>((size_t)nq * k, 0), std::vector<int32_t>((size_t)nq * k, 0),
@@ -414,7 +389,7 @@ int vs_search_groups(vs_index* ix, const vs_groups* gr, const vs_sel* sel, const
         if (gr->n_cov == 0 || (sel && sel->m == 0)) {  // nothing to rank: all padding
             stats[1] = nq;
             deliver();
-            note_stats(ix, stats, times);
+            note();
             return;
         }
         DeviceGuard dg(ix->device);
@@ -457,95 +432,52 @@ int vs_search_groups(vs_index* ix, const vs_groups* gr, const vs_sel* sel, const
         if (mb.members == 0) {
             stats[1] = nq;
             deliver();
-            note_stats(ix, stats, times);
+            note();
             return;
         }
         const int target = (int)std::min<int64_t>(k, mb.groups);
-        const int64_t first = std::min<int64_t>(set_first > 0 ? set_first : std::max<int64_t>(4 * kg, 64), limit);
-        const int64_t Lmax = std::min<int64_t>(limit, mb.members);
-        int64_t L = std::min<int64_t>(first, Lmax);
-        DevEvent e0(hipEventDefault), e1(hipEventDefault), e2(hipEventDefault);
-        std::vector<int64_t> pending((size_t)nq), next;
-        for (int64_t i = 0; i < nq; ++i) pending[(size_t)i] = i;
-        std::vector<float> qsub;
-        GrWalk w;
-        // ---- tiers 1 and 2: exact top-L lists, walked on the device --------------------------------
-        for (bool first_pass = true;; first_pass = false) {
-            const int64_t n = (int64_t)pending.size();
-            const int tier = first_pass ? 0 : 1;
-            const float* qp = q;
-            if (!first_pass) {  // the queries not complete as one batch
-                qsub.resize((size_t)n * ix->d);
-                for (int64_t j = 0; j < n; ++j)
-                    std::copy(q + pending[(size_t)j] * ix->d, q + (pending[(size_t)j] + 1) * ix->d, qsub.begin() + j * ix->d);
-                qp = qsub.data();
-            }
-            const int kk = (int)L;
-            const SelPlan plan = mb.sel ? sel_plan(ix, mb.sel, n, kk) : SelPlan{0, 0};
-            const int64_t chunk = stage_chunk(ix, n, kk, !mb.sel);
-            next.clear();
-            for (int64_t q0 = 0; q0 < n; q0 += chunk) {
-                const int64_t m = std::min(chunk, n - q0);
-                HIP_CHECK(hipEventRecord(e0, st));
-                stage_queries(ix, c, qp, q0, m, st);
-                const StagedOut so = staged_out(c, m, kk, !mb.sel);
-                if (mb.sel) sel_search_ctx(ix, c, mb.sel, plan, c->qdev.as<float>(), m, kk, SearchOut{so.Dd, so.Id}, st);
-                else search_staged(ix, c, m, kk, so, st, true);
-                HIP_CHECK(hipEventRecord(e1, st));
-                walk_lists(ix, c, gr, mb.gsize, so.Id, so.Dd, L, m, k, g, target, w, st, &e2);
-                deliver_walk(w, m, pending.data() + q0, out);
-                times.search[tier] += ms_between(e0, e1);
-                times.walk[tier] += ms_between(e1, e2);
-                for (int64_t j = 0; j < m; ++j) {
-                    const int64_t r = pending[(size_t)(q0 + j)];
-                    if (!out.complete[(size_t)r] && L < mb.members) next.push_back(r);
-                }
-            }
-            stats[5] = std::max(stats[5], L);
-            stats[first_pass ? 1 : 2] += n - (int64_t)next.size();
-            pending.swap(next);
-            if (pending.empty() || L >= Lmax) break;
-            L = std::min<int64_t>(4 * L, Lmax);
-        }
+        // ---- tiers 1 and 2: exact top-L lists, walked on the device; not complete goes deeper --------
+        std::vector<uint8_t> h;
+        const Deepened dl = deepen_lists(
+            ix, c, st, mb.sel, mb.members, depth.first, limit, q, nq, times,
+            [&](const StagedOut& so, int64_t L, int64_t m, const int64_t* idx, DevEvent* ev) {
+                deliver_walk(walk_lists(ix, c, gr, mb.gsize, so.Id, so.Dd, L, m, k, g, target, h, st, ev), m, idx, out);
+            },
+            [&](int64_t r) { return out.complete[(size_t)r] != 0; });
+        stats[1] = dl.done[0];
+        stats[2] = dl.done[1];
+        stats[5] = dl.longest;
         // ---- tier 3: restricted rounds, one query at a time -------------------------------------------
-        if (!pending.empty()) {
+        if (!dl.pending.empty()) {
             Round3 r3{ix, c, gr, mb, sel, limit, target, st};
-            for (int64_t qi : pending) {
+            for (int64_t qi : dl.pending) {
                 stats[4] += restricted_rounds(r3, q, qi, out, times, stats[5]);
                 ++stats[3];
             }
         }
         deliver();
-        note_stats(ix, stats, times);
+        note();
     });
 }
 
 int vs_set_group_depth(vs_index* ix, int32_t first, int32_t limit) {
     return guarded([&] {
         check_index(ix);
-        const int kmax = KP_MAX * 4 / 5;
-        if (first < 0 || limit < 0 || first > kmax || limit > kmax || (first > 0 && limit > 0 && first > limit))
-            throw VsError(VS_ERR_ARG, "group depth: 1 <= first <= limit <= " + std::to_string(kmax) + " (0 = default)");
-        ix->gr_first.store(first);
-        ix->gr_limit.store(limit);
+        ix->gr.set(first, limit, K_MAX, "group");
     });
 }
 
 int vs_group_last_stats(vs_index* ix, int64_t* out, int cap) {
     return guarded([&] {
         check_index(ix);
-        if (!out || cap < 0) throw VsError(VS_ERR_ARG, "bad stats buffer");
-        std::lock_guard<std::mutex> g(ix->gr_mu);
-        for (int i = 0; i < std::min(cap, 6); ++i) out[i] = ix->gr_stats[i];
+        copy_last(ix->gr.mu, ix->gr.stats, 6, out, cap, "stats");
     });
 }
 
 int vs_group_last_times(vs_index* ix, double* out, int cap) {
     return guarded([&] {
         check_index(ix);
-        if (!out || cap < 0) throw VsError(VS_ERR_ARG, "bad times buffer");
-        std::lock_guard<std::mutex> g(ix->gr_mu);
-        for (int i = 0; i < std::min(cap, 8); ++i) out[i] = ix->gr_times[i];
+        copy_last(ix->gr.mu, ix->gr.times, 8, out, cap, "times");
     });
 }
 

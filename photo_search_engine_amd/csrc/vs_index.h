@@ -1,6 +1,7 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
-// vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip).
+// vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip; the last two share
+// the list-deepening driver of vs_walk.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -69,6 +70,43 @@ struct Ctx {
     }
 };
 
+// A walk job on the index (diversified search, grouped search): the list lengths set by the caller
+// (0 = the defaults) and what the last call reported, stats[] and its HIP-event ms times[].
+struct WalkState {
+    std::atomic<int> first{0}, limit{0};
+    std::mutex mu;
+    int64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    double times[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    struct Depth { int64_t first, limit; };  // the first list's length and the longest one's
+    Depth resolve(int64_t default_first, int kmax) const {
+        const int set_first = first.load(), set_limit = limit.load();
+        const int64_t lim = set_limit > 0 ? set_limit : kmax;
+        return {std::min<int64_t>(set_first > 0 ? set_first : default_first, lim), lim};
+    }
+    void set(int new_first, int new_limit, int kmax, const char* what) {
+        const std::string rule = " depth: 1 <= first <= limit <= " + std::to_string(kmax) + " (0 = default)";
+        if (new_first < 0 || new_limit < 0 || new_first > kmax || new_limit > kmax ||
+            (new_first > 0 && new_limit > 0 && new_first > new_limit))
+            throw VsError(VS_ERR_ARG, what + rule);
+        first.store(new_first);
+        limit.store(new_limit);
+    }
+    void note(const int64_t* s, int ns, const double* t, int nt) {
+        std::lock_guard<std::mutex> g(mu);
+        std::copy(s, s + ns, stats);
+        std::copy(t, t + nt, times);
+    }
+};
+
+// the first min(n, cap) numbers a call left behind (the *_last_stats / *_last_times exports; what:
+// "stats" or "times")
+template <typename T>
+void copy_last(std::mutex& mu, const T* src, int n, T* out, int cap, const char* what) {
+    if (!out || cap < 0) throw VsError(VS_ERR_ARG, std::string("bad ") + what + " buffer");
+    std::lock_guard<std::mutex> g(mu);
+    std::copy(src, src + std::min(cap, n), out);
+}
+
 }  // namespace vs
 
 constexpr int64_t kDefaultScanLimit = 192ll << 20;  // (the MALL holds such a corpus between calls)
@@ -122,21 +160,14 @@ struct vs_index {
     std::atomic<int> range_mode{VS_RANGE_AUTO};
     std::mutex range_mu;
     int64_t range_stats[4] = {0, 0, 0, 0};
-    // diversified search: the list lengths set by vs_set_diverse_depth (0 = the defaults); the last
-    // call's {queries, complete after the first list, after a deeper list, answered from the full
-    // ranking, longest list walked} (vs_diverse_last_stats)
-    std::atomic<int> dv_first{0}, dv_limit{0};
-    std::mutex dv_mu;
-    int64_t dv_stats[5] = {0, 0, 0, 0, 0};
-    double dv_times[6] = {0, 0, 0, 0, 0, 0};  // ... and its HIP-event ms {search, walk} per tier (vs_diverse_last_times)
-    // grouped search: the list lengths set by vs_set_group_depth (0 = the defaults); the last call's
-    // {queries, complete after the first list, after a deeper list, finished by restricted rounds,
-    // restricted rounds run, longest list walked} (vs_group_last_stats) and its HIP-event ms
-    // (vs_group_last_times)
-    std::atomic<int> gr_first{0}, gr_limit{0};
-    std::mutex gr_mu;
-    int64_t gr_stats[6] = {0, 0, 0, 0, 0, 0};
-    double gr_times[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // diversified search (vs_set_diverse_depth): the last call's {queries, complete after the first
+    // list, after a deeper list, answered from the full ranking, longest list walked}
+    // (vs_diverse_last_stats) and its ms {search, walk} per tier (vs_diverse_last_times)
+    vs::WalkState dv;
+    // grouped search (vs_set_group_depth): the last call's {queries, complete after the first list,
+    // after a deeper list, finished by restricted rounds, restricted rounds run, longest list walked}
+    // (vs_group_last_stats) and its ms {search, walk} per tier, restrict, compact (vs_group_last_times)
+    vs::WalkState gr;
     int last_kernel_kind = 0;  // 1 = mfma, 2 = gemv, 3 = int8 mfma, 4 = int8 gemv, 5 = exact full scan
     // Screen health (first passes of MFMA batches): the certificate-failure count of a batch is read
     // back without a host wait (pinned word + event, observed by a later search).  A failed query
@@ -223,6 +254,12 @@ inline void check_index(const vs_index* ix) {
     if (!ix) throw VsError(VS_ERR_ARG, "null index");
 }
 
+// one radius per query, none of them NaN
+inline void check_radii(const float* radius, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (std::isnan(radius[i])) throw VsError(VS_ERR_ARG, "radius is NaN (query " + std::to_string(i) + ")");
+}
+
 // Points a leased Ctx's full-scan counter at the caller's device word for one call, and
 // clears it on every exit (exceptions included), before the Ctx returns to the pool: a later
 // lease must never count into a buffer it does not own.
@@ -280,30 +317,23 @@ void search_all(vs_index* ix, Ctx* c, const float* q, int64_t nq, int k, int Kp,
 ScreenArgs mfma_screen_base(const vs_index* ix, bool i8);
 void mfma_workspace(Ctx* c, ScreenArgs& a);
 float xmax_of(const vs_index* ix);  // upper bound on ||x|| over the shard (RefineArgs::xmax)
-void check_k(int k, int kmax = KP_MAX * 4 / 5);
+void check_k(int k, int kmax = K_MAX);
 // host entry points: queries and results pass through pinned staging of at most kPinnedStageCap
 // bytes per context, in chunks of queries (whole MFMA batches when a chunk holds more than one)
 int64_t stage_chunk(const vs_index* ix, int64_t nq, int kk, bool with_cert);
 void stage_queries(const vs_index* ix, Ctx* c, const float* q, int64_t q0, int64_t m, hipStream_t st);
-// a chunk's device and pinned host result blocks, one layout [I int64 | D fp32 | cert int]
+// a chunk's device and pinned host result blocks, one layout [I int64 | D fp32 | cert int] (exact_lists)
 struct StagedOut {
     int64_t *Id, *Ik;
     float *Dd, *Dk;
     int *cert_d, *cert_h;
     size_t bytes;
+    int64_t redo;  // exact_lists: the queries the selector's overfetch tier left short and its scan re-answered
 };
-StagedOut staged_out(Ctx* c, int64_t m, int kk, bool with_cert);
-void fetch_staged(Ctx* c, const StagedOut& o, hipStream_t st);  // ONE D2H copy, then the stream is waited for
 float worst_score(const vs_index* ix);
 void fill_padding(float* D, int64_t* I, int64_t n, float fillD);
 // [m][kk] staged results -> the caller's [..][k] rows from q0 on, padded past kk (faiss layout)
 void scatter_padded(const StagedOut& o, int64_t q0, int64_t m, int k, int kk, float fillD, float* D, int64_t* I);
-
-// vs_search's road from a staged chunk on: the m queries in c->qdev searched at depth kk into so's
-// device block, fetched to its host block, certificate failures re-searched one by one (4x deeper
-// screens, then the exact full scan) into the host block -- and, with mirror, into the device block
-// too (a kernel reads the lists afterwards).  Synchronises st.
-void search_staged(vs_index* ix, Ctx* c, int64_t m, int kk, const StagedOut& so, hipStream_t st, bool mirror);
 
 // ---- vs_sel_host.hip ----
 void check_sel(const vs_index* ix, const vs_sel* sel);
@@ -318,6 +348,14 @@ SelPlan sel_plan(const vs_index* ix, const vs_sel* sel, int64_t nq, int k);
 int64_t sel_search_ctx(vs_index* ix, Ctx* c, const vs_sel* sel, const SelPlan& plan, const float* q, int64_t nq, int k,
                        const SearchOut& out, hipStream_t st);
 void sel_note_stats(vs_index* ix, const vs_sel* sel, const SelPlan& plan, int64_t redo);
+
+// vs_search.hip -- one road from a staged chunk to exact lists: the m queries in c->qdev ranked at depth
+// kk over the members of sel (plan: its sel_plan for the call) or over every row (sel null) into the
+// chunk's blocks, valid afterwards where want says: LISTS_HOST (Ik / Dk; the stream is waited for) and /
+// or LISTS_DEVICE (Id / Dd: a kernel reads them).  The selector road's re-answered count is in redo.
+enum : unsigned { LISTS_HOST = 1, LISTS_DEVICE = 2 };
+StagedOut exact_lists(vs_index* ix, Ctx* c, const vs_sel* sel, const SelPlan& plan, int64_t m, int kk, unsigned want,
+                      hipStream_t st);
 
 // ---- vs_range_host.hip ----
 struct RangeStats {

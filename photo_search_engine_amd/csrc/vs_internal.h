@@ -39,6 +39,8 @@ static_assert(MFMA_KP_MAX + TR <= MFMA_CAP, "MFMA screen: compaction invariant c
 constexpr int GEMV_NQ_MAX = 8; // queries per GEMV screen launch
 constexpr int GEMV_SPLIT = 4;   // row blocks per tile of the GEMV screen's small-corpus work items
 constexpr int KP_MAX = 4096;   // largest screening depth (k <= 3276; k_refine sorts 4096 keys in LDS)
+// the largest k of an exact search: its screen lists k + k / 4 rows (screen_depth), KP_MAX at the most
+constexpr int K_MAX = KP_MAX * 4 / 5;
 constexpr int SELECT_E = 16;   // keys per thread in block selection (256 threads -> 4096 keys)
 
 inline int es_of(int dt) { return dt == DT_F32 ? 4 : 2; }
@@ -587,7 +589,7 @@ hipError_t launch_km_finalize(const double* P, const int64_t* segoff, const unsi
 // ---- diversified search (vs_diverse.hip) ---------------------------------------------
 constexpr int DV_THREADS = 256;           // k_diverse_walk: one workgroup per query
 constexpr int DV_BLOCK = 64;              // candidates resolved per step of the walk
-constexpr int DV_K_MAX = KP_MAX * 4 / 5;  // accepted rows kept in LDS (vs_search's k limit)
+constexpr int DV_K_MAX = K_MAX;  // accepted rows kept in LDS (vs_search's k limit)
 struct DiverseArgs {
     const uint8_t* corpus;  // tiled shard
     int d, dpad, dt, metric;
@@ -614,7 +616,7 @@ hipError_t launch_diverse_walk(const DiverseArgs& a, int nq, hipStream_t st);
 // non-negative keys, ascending; < 0 an ungrouped row, ~code its index among the ungrouped keys.
 constexpr int GR_THREADS = 64;            // k_group_walk: one wave per query
 constexpr int GR_BLOCK = 64;              // candidates loaded per step of the walk
-constexpr int GR_K_MAX = KP_MAX * 4 / 5;  // group slots kept in LDS (vs_search's k limit)
+constexpr int GR_K_MAX = K_MAX;  // group slots kept in LDS (vs_search's k limit)
 constexpr int GR_TABLE = 8192;            // open-address table of identified groups (>= 2.5 GR_K_MAX)
 constexpr int GR_NONE = -0x7FFFFFFF - 1;  // slot_code of an unused slot
 struct GroupWalkArgs {

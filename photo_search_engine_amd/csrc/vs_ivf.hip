@@ -677,8 +677,8 @@ void check_search_args(const vs_ivf* ix, int64_t nq, int32_t k, int32_t nprobe) 
     check_ivf(ix);
     if (nq < 0) throw VsError(VS_ERR_ARG, "nq must be >= 0");
     if (k <= 0) throw VsError(VS_ERR_ARG, "k must be > 0");
-    if (screen_depth(k) < k || k > KP_MAX * 4 / 5)
-        throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(KP_MAX * 4 / 5) + ")");
+    if (screen_depth(k) < k || k > K_MAX)
+        throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(K_MAX) + ")");
     if (nprobe <= 0) throw VsError(VS_ERR_ARG, "nprobe must be > 0");
     if (!ix->trained) throw VsError(VS_ERR_ARG, "IVF index is not trained (set its centroids first)");
 }

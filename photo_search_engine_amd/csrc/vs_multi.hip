@@ -466,7 +466,7 @@ int vs_multi_search(vs_multi* m, const float* q, int64_t nq, int32_t k, float* D
             }
             return;
         }
-        if (kk > KP_MAX * 4 / 5) throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(KP_MAX * 4 / 5) + ")");
+        if (kk > K_MAX) throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(K_MAX) + ")");
         const int G = m->G;
         const size_t lb = (size_t)nq * kk;
         CtxLease L(m);
@@ -560,7 +560,7 @@ int vs_multi_search_sel(vs_multi* m, const uint8_t* bitmap, int64_t nbytes, cons
             }
             return;
         }
-        if (kk > KP_MAX * 4 / 5) throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(KP_MAX * 4 / 5) + ")");
+        if (kk > K_MAX) throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(K_MAX) + ")");
         const int G = m->G;
         const size_t lb = (size_t)nq * kk;
         constexpr int64_t kChunkBytes = kChunk / 8;

@@ -244,8 +244,7 @@ void vs::range_search_host(vs_index* ix, const vs_sel* sel, const float* q, int6
         return;
     }
     if (!q || !radius) throw VsError(VS_ERR_ARG, "null host buffer");
-    for (int64_t i = 0; i < nq; ++i)
-        if (std::isnan(radius[i])) throw VsError(VS_ERR_ARG, "radius is NaN (query " + std::to_string(i) + ")");
+    check_radii(radius, nq);
     if (ix->ntotal == 0 || (sel && sel->m == 0)) {  // nothing to return
         range_note_stats(ix, stt);
         return;
@@ -308,9 +307,7 @@ int vs_set_range_mode(vs_index* ix, int mode) {
 int vs_range_last_stats(vs_index* ix, int64_t* out, int cap) {
     return guarded([&] {
         check_index(ix);
-        if (!out || cap < 0) throw VsError(VS_ERR_ARG, "bad stats buffer");
-        std::lock_guard<std::mutex> g(ix->range_mu);
-        for (int i = 0; i < std::min(cap, 4); ++i) out[i] = ix->range_stats[i];
+        copy_last(ix->range_mu, ix->range_stats, 4, out, cap, "stats");
     });
 }
 

@@ -81,13 +81,8 @@ int vs_search_rows(vs_index* ix, const vs_sel* sel, const int64_t* ids, int64_t 
         for (int64_t q0 = 0; q0 < n; q0 += chunk) {
             const int64_t m = std::min(chunk, n - q0);
             gather_queries(ix, c, ids_dev + q0, m, st);
-            StagedOut so = staged_out(c, m, kk, !sel);
-            if (sel) {
-                redo += sel_search_ctx(ix, c, sel, plan, c->qdev.as<float>(), m, kk, SearchOut{so.Dd, so.Id}, st);
-                if (!drop) fetch_staged(c, so, st);
-            } else {
-                search_staged(ix, c, m, kk, so, st, drop);
-            }
+            const StagedOut so = exact_lists(ix, c, sel, plan, m, kk, drop ? LISTS_DEVICE : LISTS_HOST, st);
+            redo += so.redo;
             if (!drop) {
                 scatter_padded(so, q0, m, k, kk, fillD, D, I);
                 continue;
@@ -137,8 +132,7 @@ int vs_range_search_rows(vs_index* ix, const vs_sel* sel, const int64_t* ids, in
             return;
         }
         if (!radius) throw VsError(VS_ERR_ARG, "null host buffer");
-        for (int64_t i = 0; i < n; ++i)
-            if (std::isnan(radius[i])) throw VsError(VS_ERR_ARG, "radius is NaN (query " + std::to_string(i) + ")");
+        check_radii(radius, n);
         if (ids) check_row_ids(ix, ids, n);
         if (sel && sel->m == 0) {  // nothing to return
             range_note_stats(ix, stt);

@@ -954,7 +954,7 @@ void vs::search_pending_free(vs_pending* p) { delete p; }
 namespace vs {
 
 void check_k(int k, int kmax) {
-    if (k > kmax) throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(KP_MAX * 4 / 5) + ")");
+    if (k > kmax) throw VsError(VS_ERR_ARG, "k too large (max " + std::to_string(K_MAX) + ")");
 }
 
 // The caller's buffers are pageable: a huge batch never pins its whole size for the index's life.
@@ -976,7 +976,7 @@ void stage_queries(const vs_index* ix, Ctx* c, const float* q, int64_t q0, int64
     HIP_CHECK(hipMemcpyAsync(c->qdev.p, c->hq.p, bytes, hipMemcpyHostToDevice, st));
 }
 
-StagedOut staged_out(Ctx* c, int64_t m, int kk, bool with_cert) {
+static StagedOut staged_out(Ctx* c, int64_t m, int kk, bool with_cert) {
     StagedOut o{};
     o.bytes = (size_t)m * kk * (sizeof(int64_t) + sizeof(float)) + (with_cert ? (size_t)m * sizeof(int) : 0);
     c->hout.ensure(o.bytes);
@@ -992,7 +992,7 @@ StagedOut staged_out(Ctx* c, int64_t m, int kk, bool with_cert) {
     return o;
 }
 
-void fetch_staged(Ctx* c, const StagedOut& o, hipStream_t st) {
+static void fetch_staged(Ctx* c, const StagedOut& o, hipStream_t st) {
     HIP_CHECK(hipMemcpyAsync(c->hout.p, c->outAll.p, o.bytes, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
 }
@@ -1016,7 +1016,11 @@ void scatter_padded(const StagedOut& o, int64_t q0, int64_t m, int k, int kk, fl
     }
 }
 
-void search_staged(vs_index* ix, Ctx* c, int64_t m, int kk, const StagedOut& so, hipStream_t st, bool mirror) {
+// vs_search's road from a staged chunk on: the m queries in c->qdev searched at depth kk into so's
+// device block, fetched to its host block, certificate failures re-searched one by one (4x deeper
+// screens, then the exact full scan) into the host block -- and, with mirror, into the device block
+// too (a kernel reads the lists afterwards).  Synchronises st.
+static void search_staged(vs_index* ix, Ctx* c, int64_t m, int kk, const StagedOut& so, hipStream_t st, bool mirror) {
     c->outD.ensure((size_t)kk * sizeof(float));
     c->outI.ensure((size_t)kk * sizeof(int64_t));
     c->cert.ensure(sizeof(int));
@@ -1049,6 +1053,18 @@ void search_staged(vs_index* ix, Ctx* c, int64_t m, int kk, const StagedOut& so,
             HIP_CHECK(hipStreamSynchronize(st));
         }
     }
+}
+
+StagedOut exact_lists(vs_index* ix, Ctx* c, const vs_sel* sel, const SelPlan& plan, int64_t m, int kk, unsigned want,
+                      hipStream_t st) {
+    StagedOut so = staged_out(c, m, kk, !sel);
+    if (!sel) {  // (the host block is fetched either way: the certificates are read there)
+        search_staged(ix, c, m, kk, so, st, (want & LISTS_DEVICE) != 0);
+        return so;
+    }
+    so.redo = sel_search_ctx(ix, c, sel, plan, c->qdev.as<float>(), m, kk, SearchOut{so.Dd, so.Id}, st);
+    if (want & LISTS_HOST) fetch_staged(c, so, st);
+    return so;
 }
 
 }  // namespace vs
@@ -1144,8 +1160,7 @@ int vs_search(vs_index* ix, const float* q, int64_t nq, int32_t k, float* D, int
         for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
             const int64_t m = std::min(chunk, nq - q0);
             stage_queries(ix, c, q, q0, m, st);
-            const StagedOut so = staged_out(c, m, kk, true);
-            search_staged(ix, c, m, kk, so, st, false);
+            const StagedOut so = exact_lists(ix, c, nullptr, SelPlan{0, 0}, m, kk, LISTS_HOST, st);
             scatter_padded(so, q0, m, k, kk, fillD, D, I);
         }
     });

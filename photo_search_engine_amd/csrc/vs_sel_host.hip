@@ -47,16 +47,15 @@ constexpr double kSelScanFactor = 3.0;
 namespace vs {
 
 SelPlan sel_plan(const vs_index* ix, const vs_sel* sel, int64_t nq, int k) {
-    const int kmax = KP_MAX * 4 / 5;
     const int mode = ix->sel_mode.load();
     // (k > ntotal: a shard of a multi-device index with fewer rows than k; the scan pads)
     if (sel->m == 0 || mode == VS_SEL_SCAN || k > ix->ntotal) return {VS_SEL_SCAN, 0};
     const double want = std::ceil(1.5 * (double)k * (double)ix->ntotal / (double)sel->m) + 32.0;
     const int64_t raw = want >= 1e15 ? (int64_t)1e15 : round_up((int64_t)want, 16);
-    // (k <= k': ntotal >= m, k <= ntotal here and the callers keep k <= kmax)
-    const int kp = (int)std::min<int64_t>(std::min<int64_t>(kmax, ix->ntotal), raw);
+    // (k <= k': ntotal >= m, k <= ntotal here and the callers keep k <= K_MAX)
+    const int kp = (int)std::min<int64_t>(std::min<int64_t>(K_MAX, ix->ntotal), raw);
     if (mode == VS_SEL_OVERFETCH) return {VS_SEL_OVERFETCH, kp};
-    if (nq <= 2 || (double)nq * (double)sel->m <= kSelScanFactor * (double)ix->ntotal || raw > kmax)
+    if (nq <= 2 || (double)nq * (double)sel->m <= kSelScanFactor * (double)ix->ntotal || raw > K_MAX)
         return {VS_SEL_SCAN, 0};
     return {VS_SEL_OVERFETCH, kp};
 }
@@ -156,7 +155,7 @@ void vs::search_sel_device(vs_index* ix, const vs_sel* sel, const float* q_dev, 
     DeviceGuard dg(ix->device);
     check_sel(ix, sel);
     if (k <= 0) throw VsError(VS_ERR_ARG, "k must be > 0");
-    if (ix->ntotal == 0 || k > KP_MAX * 4 / 5) throw VsError(VS_ERR_ARG, "empty index or k too large");
+    if (ix->ntotal == 0 || k > K_MAX) throw VsError(VS_ERR_ARG, "empty index or k too large");
     if (nq > 0x7FFFFFFF / 3) throw VsError(VS_ERR_ARG, "too many queries in one call");
     CtxLease L(ix, st, false);
     const SelPlan plan = sel_plan(ix, sel, nq, k);
@@ -232,9 +231,7 @@ int vs_set_sel_mode(vs_index* ix, int mode) {
 int vs_sel_last_stats(vs_index* ix, int64_t* out, int cap) {
     return guarded([&] {
         check_index(ix);
-        if (!out || cap < 0) throw VsError(VS_ERR_ARG, "bad stats buffer");
-        std::lock_guard<std::mutex> g(ix->sel_mu);
-        for (int i = 0; i < std::min(cap, 4); ++i) out[i] = ix->sel_stats[i];
+        copy_last(ix->sel_mu, ix->sel_stats, 4, out, cap, "stats");
     });
 }
 
@@ -267,9 +264,8 @@ int vs_search_sel(vs_index* ix, const vs_sel* sel, const float* q, int64_t nq, i
         for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
             const int64_t m = std::min(chunk, nq - q0);
             stage_queries(ix, c, q, q0, m, st);
-            const StagedOut so = staged_out(c, m, kk, false);
-            redo += sel_search_ctx(ix, c, sel, plan, c->qdev.as<float>(), m, kk, SearchOut{so.Dd, so.Id}, st);
-            fetch_staged(c, so, st);
+            const StagedOut so = exact_lists(ix, c, sel, plan, m, kk, LISTS_HOST, st);
+            redo += so.redo;
             scatter_padded(so, q0, m, k, kk, fillD, D, I);
         }
         sel_note_stats(ix, sel, plan, redo);

@@ -8,6 +8,7 @@ hand in torch tensors' ``data_ptr()`` without torch types crossing the C ABI.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Optional, Tuple
@@ -398,6 +399,26 @@ class FlatIndex:
         self.dtype = dtype
         self.device = int(device)
 
+    def _queries(self, q, name: str) -> np.ndarray:
+        """``q`` as a contiguous fp32 ``(nq, d)`` array (``name``: the calling method, for the error)."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"{name} expects an (nq, {self.d}) array, got {q.shape}")
+        return q
+
+    @contextlib.contextmanager
+    def _sel(self, sel):
+        """``(selector, handle)`` for one call: ``sel`` itself, a temporary :class:`Selector` made from a mask
+        or row ids and closed on exit, or ``(None, None)``.  A closed selector is an argument error."""
+        s = sel if sel is None or isinstance(sel, Selector) else Selector(self, sel)
+        try:
+            if s is not None and s._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            yield s, (None if s is None else s._h)
+        finally:
+            if s is not sel:
+                s.close()
+
     # -- faiss-like surface ------------------------------------------------------------------
     @property
     def ntotal(self) -> int:
@@ -413,9 +434,7 @@ class FlatIndex:
         """Exact top-``k``; with ``sel`` (a :class:`Selector`, a boolean mask or row ids) the exact
         top-``k`` among the allowed rows -- faiss's ``search(q, k, params=SearchParameters(sel=...))``
         -- padded with ``-1`` / the worst score when fewer than ``k`` rows are allowed."""
-        q = np.ascontiguousarray(q, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search expects an (nq, {self.d}) array, got {q.shape}")
+        q = self._queries(q, "search")
         nq = q.shape[0]
         k = int(k)
         if k <= 0:
@@ -425,15 +444,8 @@ class FlatIndex:
         if sel is None:
             check(self._L.vs_search(self._h, _ptr(q), nq, k, _ptr(D), _ptr(I)))
             return D, I
-        own = None if isinstance(sel, Selector) else Selector(self, sel)
-        s = own or sel
-        try:
-            if s._h is None:
-                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
-            check(self._L.vs_search_sel(self._h, s._h, _ptr(q), nq, k, _ptr(D), _ptr(I)))
-        finally:
-            if own is not None:
-                own.close()
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_search_sel(self._h, sh, _ptr(q), nq, k, _ptr(D), _ptr(I)))
         return D, I
 
     def range_search(self, q, radius, sel=None, max_total: Optional[int] = None):
@@ -442,25 +454,15 @@ class FlatIndex:
         ``(lims, D, I)``, query ``i``'s rows at ``[lims[i], lims[i + 1])`` best first -- the first
         entries of ``search(q, k)``.  ``sel`` as in :meth:`search`; ``max_total`` caps the number of
         results (beyond it the call raises, naming the count)."""
-        q = np.ascontiguousarray(q, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"range_search expects an (nq, {self.d}) array, got {q.shape}")
+        q = self._queries(q, "range_search")
         nq = q.shape[0]
         r = range_radius(radius, nq)
         cap = 0 if max_total is None else int(max_total)
         if max_total is not None and cap <= 0:
             raise ValueError("max_total must be > 0")
-        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
-        s = own or sel
         h = ctypes.c_void_p()
-        try:
-            if s is not None and s._h is None:
-                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
-            check(self._L.vs_range_search(self._h, s._h if s is not None else None, _ptr(q), nq, _ptr(r), cap,
-                                          ctypes.byref(h)))
-        finally:
-            if own is not None:
-                own.close()
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_range_search(self._h, sh, _ptr(q), nq, _ptr(r), cap, ctypes.byref(h)))
         return _take_range_result(self._L, h, nq)
 
     def search_rows(self, ids, k: int, sel=None, drop_self: bool = True) -> Tuple[np.ndarray, np.ndarray]:
@@ -478,16 +480,9 @@ class FlatIndex:
             raise _lib.VsError(_lib.VS_ERR_ARG, "k must be > 0")
         D = np.empty((n, k), dtype=np.float32)
         I = np.empty((n, k), dtype=np.int64)
-        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
-        s = own or sel
-        try:
-            if s is not None and s._h is None:
-                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
-            check(self._L.vs_search_rows(self._h, s._h if s is not None else None, _ptr(ids), n, k,
-                                         SELF_MODES["drop" if drop_self else "keep"], _ptr(D), _ptr(I)))
-        finally:
-            if own is not None:
-                own.close()
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_search_rows(self._h, sh, _ptr(ids), n, k, SELF_MODES["drop" if drop_self else "keep"],
+                                         _ptr(D), _ptr(I)))
         return D, I
 
     def range_search_rows(self, radius, ids=None, sel=None, self_mode: str = "above",
@@ -507,18 +502,10 @@ class FlatIndex:
         ids = None if ids is None else row_ids(ids, self.ntotal)
         n = self.ntotal if ids is None else ids.shape[0]
         r = range_radius(radius, n)
-        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
-        s = own or sel
         h = ctypes.c_void_p()
-        try:
-            if s is not None and s._h is None:
-                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
-            check(self._L.vs_range_search_rows(self._h, s._h if s is not None else None,
-                                               _ptr(ids) if ids is not None else None, n, _ptr(r),
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_range_search_rows(self._h, sh, _ptr(ids) if ids is not None else None, n, _ptr(r),
                                                SELF_MODES[self_mode], cap, ctypes.byref(h)))
-        finally:
-            if own is not None:
-                own.close()
         return _take_range_result(self._L, h, n)
 
     def _kmeans_call(self, s, k: int, niter: int, metric: int, c: np.ndarray, m: int) -> KMeansResult:
@@ -553,37 +540,23 @@ class FlatIndex:
         if int(niter) < 0:
             raise ValueError("niter must be >= 0")
         kmeans_check_init(init, int(k), self.d)
-        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
-        s = own or sel
-        try:
-            if s is not None and s._h is None:
-                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+        with self._sel(sel) as (s, _):
             members = self._members(s)
             k, niter = kmeans_args(k, niter, members.shape[0])
             c = kmeans_init(init, k, self.d, seed, members, self.reconstruct).copy()
             return self._kmeans_call(s, k, niter, code, c, members.shape[0])
-        finally:
-            if own is not None:
-                own.close()
 
     def assign_rows(self, centroids, sel=None, metric=None) -> Tuple[np.ndarray, np.ndarray]:
         """The ``niter = 0`` form of :meth:`kmeans`: ``(labels, distances)`` of the members against the
         given centroids -- bit-equal to ``search(reconstruct rows, 1)`` on a flat index of them."""
         code = kmeans_metric(metric, self.metric_type)
         c = kmeans_centroids(centroids, self.d).copy()
-        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
-        s = own or sel
-        try:
-            if s is not None and s._h is None:
-                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+        with self._sel(sel) as (s, _):
             m = self.ntotal if s is None else s.count
             if c.shape[0] > m:
                 raise ValueError(f"k = {c.shape[0]} exceeds the {m} members")
             r = self._kmeans_call(s, c.shape[0], 0, code, c, m)
             return r.labels, r.distances
-        finally:
-            if own is not None:
-                own.close()
 
     def search_diverse(self, q, k: int, radius, sel=None) -> DiverseResult:
         """Exact top-``k`` with near-duplicates collapsed (``vs_search_diverse``, include/vs.h): the
@@ -592,9 +565,7 @@ class FlatIndex:
         radius`` squared L2 -- the predicate of :meth:`range_search_rows`; a scalar or one value per
         query); otherwise it counts as hidden under the earliest-accepted row it is near.  ``sel`` as
         in :meth:`search`.  Returns a :class:`DiverseResult`."""
-        q = np.ascontiguousarray(q, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search_diverse expects an (nq, {self.d}) array, got {q.shape}")
+        q = self._queries(q, "search_diverse")
         nq = q.shape[0]
         k = int(k)
         if k <= 0:
@@ -604,16 +575,9 @@ class FlatIndex:
         I = np.empty((nq, k), dtype=np.int64)
         hidden = np.zeros((nq, k), dtype=np.int32)
         examined = np.zeros((nq,), dtype=np.int64)
-        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
-        s = own or sel
-        try:
-            if s is not None and s._h is None:
-                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
-            check(self._L.vs_search_diverse(self._h, s._h if s is not None else None, _ptr(q), nq, k, _ptr(r), _ptr(D),
-                                            _ptr(I), _ptr(hidden), _ptr(examined)))
-        finally:
-            if own is not None:
-                own.close()
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_search_diverse(self._h, sh, _ptr(q), nq, k, _ptr(r), _ptr(D), _ptr(I), _ptr(hidden),
+                                            _ptr(examined)))
         return DiverseResult(D, I, hidden, examined)
 
     def set_diverse_depth(self, first: int = 0, limit: int = 0) -> None:
@@ -648,9 +612,7 @@ class FlatIndex:
         those of them it allows -- are ranked as :meth:`search` ranks them, the groups are ordered by
         their best member and each comes with its best members in ranking order.  ``sel`` as in
         :meth:`search`.  Returns a :class:`GroupedResult`."""
-        q = np.ascontiguousarray(q, dtype=np.float32)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search_groups expects an (nq, {self.d}) array, got {q.shape}")
+        q = self._queries(q, "search_groups")
         if not isinstance(groups, Groups):
             raise TypeError("groups must be a Groups object (FlatIndex.group_keys)")
         nq = q.shape[0]
@@ -662,18 +624,11 @@ class FlatIndex:
         I = np.empty((nq, k, g), dtype=np.int64)
         found = np.zeros((nq, k), dtype=np.int32)
         sizes = np.zeros((nq, k), dtype=np.int64)
-        own = None if sel is None or isinstance(sel, Selector) else Selector(self, sel)
-        s = own or sel
-        try:
-            if s is not None and s._h is None:
-                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+        with self._sel(sel) as (_, sh):
             if groups._h is None:
                 raise _lib.VsError(_lib.VS_ERR_ARG, "groups are closed")
-            check(self._L.vs_search_groups(self._h, groups._h, s._h if s is not None else None, _ptr(q), nq, k, g,
-                                           _ptr(keys), _ptr(D), _ptr(I), _ptr(found), _ptr(sizes)))
-        finally:
-            if own is not None:
-                own.close()
+            check(self._L.vs_search_groups(self._h, groups._h, sh, _ptr(q), nq, k, g, _ptr(keys), _ptr(D), _ptr(I),
+                                           _ptr(found), _ptr(sizes)))
         return GroupedResult(keys, D, I, found, sizes)
 
     def set_group_depth(self, first: int = 0, limit: int = 0) -> None:

@@ -93,3 +93,11 @@ def burst_corpus(d: int = 72, nbase: int = 40, nq: int = 8, seed: int = 7):
     x.setflags(write=False)
     q.setflags(write=False)
     return x, q
+
+
+def staged_chunk(L: int, d: int) -> int:
+    """Queries of one staged chunk of a search at list depth ``L`` without a selector: 8 MiB of pinned
+    staging, per query the larger of its fp32 row and its list (int64 id + fp32 score per entry, one
+    certificate); from 256 queries on, whole batches of 256."""
+    chunk = max(1, (8 << 20) // max(4 * d, 12 * L + 4))
+    return chunk // 256 * 256 if chunk >= 256 else chunk

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from oracle_diverse_index import burst_corpus, diverse_reference, oracle_diverse_factory
+from oracle_diverse_index import burst_corpus, diverse_reference, oracle_diverse_factory, staged_chunk
 
 pytestmark = pytest.mark.gpu
 
@@ -295,6 +295,42 @@ def test_batch_of_300_and_workspace_accounting(idx):
     _eq(ix.search_diverse(q300, 10, rr), ref_r, "300 queries again")
     assert ix.diverse_last_stats()["full"] > 0  # the call went through tier 3's own buffers
     assert int(L.vs_device_bytes_live()) == before
+
+
+def test_tiers_run_over_several_staged_chunks(idx):
+    """Lists of 1400 rows make a staged chunk 256 queries (8 MiB of pinned staging, 12 L + 4 bytes per
+    query), so 300 queries take two.  Radii: under -inf everything is near and under 0.05 most rows are,
+    so such a query stays short past 350 rows (it ends within 1400, or when its list holds every row);
+    every seventh query has the ordinary radius and ends in the first list.  The three radii follow
+    patterns of period 7 and 3 over queries of period 8, so a chunk that starts at query 256, or at
+    pending query 256, and reads its radii from the wrong offset gets another answer.  Depths
+    (1400, 1400): tier 1 runs over chunks of 256 + 44.  Depths (350, 1400): tier 1 is one chunk, and the
+    258 queries left, which are no prefix of the batch, go through tier 2 as 256 + 2."""
+    x, q = burst_corpus(nbase=216)
+    x = np.ascontiguousarray(x[:1400])  # (L = 1400 then holds every member: nothing is left to tier 3)
+    xs = O.round_dtype(x, "bf16")
+    n, k = x.shape[0], 10
+    i = np.arange(300)
+    rr = np.where(i % 7 == 6, _radius("ip"), np.where(i % 3 == 0, np.float32(0.05), np.float32(-np.inf))).astype(np.float32)
+    q300 = np.ascontiguousarray(np.tile(q, (38, 1))[:300])
+    by_radius = {r: diverse_reference(xs, q, k, r, "ip") for r in np.unique(rr).tolist()}  # (8 queries each)
+    ref = tuple(np.stack([by_radius[float(rr[j])][a][j % 8] for j in range(300)]) for a in range(4))
+    accepted = (ref[1] >= 0).sum(axis=1)
+    want = {depths: _tiers(ref[3], accepted, k, *depths, n) for depths in ((1400, 1400), (350, 1400))}
+    # conditions, from the reference alone: both tier loops run over more than one chunk of 256, and the
+    # radii (and with them the answers) of the second chunk differ from those at the same offsets of the first
+    assert n == 1400 and staged_chunk(1400, D_) == 256 and staged_chunk(350, D_) >= 300
+    assert want[(1400, 1400)] == (300, 0, 0)
+    assert want[(350, 1400)][0] >= 1 and want[(350, 1400)][1] >= 257 and want[(350, 1400)][2] == 0
+    pending = np.flatnonzero(~((accepted == k) & (ref[3] <= 350)))
+    assert pending.shape[0] == want[(350, 1400)][1] and (pending != np.arange(pending.shape[0])).any()
+    assert (rr[256:] != rr[:44]).any() and (rr[pending[256:]] != rr[pending[:pending.shape[0] - 256]]).any()
+    ix = _index(idx, x, "bf16", "ip")
+    for depths in ((1400, 1400), (350, 1400)):
+        ix.set_diverse_depth(*depths)
+        _eq(ix.search_diverse(q300, k, rr), ref, f"300 queries, lists of 1400, depths {depths}")
+        st = ix.diverse_last_stats()
+        assert (st["first"], st["deeper"], st["full"]) == want[depths] and st["longest"] == 1400, (st, want[depths])
 
 
 @pytest.mark.parametrize("index_type,metric", [("flat", "cosine"), ("hnsw", "l2")])

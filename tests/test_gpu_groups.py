@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from oracle_diverse_index import burst_corpus
+from oracle_diverse_index import burst_corpus, staged_chunk
 from oracle_group_index import KEY_PAD, burst_keys, expected_rounds, group_reference, oracle_group_factory
 
 pytestmark = pytest.mark.gpu
@@ -410,6 +410,44 @@ def test_batch_of_300_and_workspace_accounting(idx):
     again = ix.group_keys(_keys("giant"))
     assert int(L.vs_device_bytes_live()) == with_groups
     again.close()
+
+
+def test_tiers_run_over_several_staged_chunks(idx):
+    """Lists of 1400 rows make a staged chunk 256 queries (8 MiB of pinned staging, 12 L + 4 bytes per
+    query), so 300 queries take two.  Key scheme: as in "mixed" every fifth burst is taken apart, but its
+    rows are dealt over keys of three rows each that lie anywhere in a ranking; a query that meets one
+    of them among its first ten groups is complete only near the end of the list.  Of the eight distinct
+    queries the last meets none.  Depths (1400, 1400): tier 1 runs over chunks of 256 + 44.  Depths
+    (350, 1400): tier 1 is one chunk, and the 263 queries left, which are no prefix of the batch, go
+    through tier 2 as 256 + 7."""
+    x, q = burst_corpus(nbase=216, nq=10)
+    x, q = np.ascontiguousarray(x[:1400]), q[2:]  # (L = 1400 then holds every member: no restricted rounds)
+    xs = O.round_dtype(x, "bf16")
+    n, k, g = x.shape[0], 10, 3
+    burst = burst_keys(nbase=216)[:n]
+    apart = burst % 5 == 0
+    keys = np.ascontiguousarray(np.where(apart, BASE + 10 ** 6 + np.cumsum(apart) % (int(apart.sum()) // 3), burst + BASE))
+    q300 = np.ascontiguousarray(np.tile(q, (38, 1))[:300])
+    ref = tuple(np.tile(a, (38,) + (1,) * (a.ndim - 1))[:300] for a in group_reference(xs, q, keys, k, g, "ip"))
+    need = ref[5]
+    want = {}
+    for first, limit in ((1400, 1400), (350, 1400)):
+        done0, done1 = (need <= first) | (first >= n), (need <= limit) | (limit >= n)
+        want[(first, limit)] = (int(done0.sum()), int((done1 & ~done0).sum()), int((~done1).sum()), 0)
+    # conditions, from the reference alone: both tier loops run over more than one chunk of 256
+    assert n == 1400 and staged_chunk(1400, D_) == 256 and staged_chunk(350, D_) >= 300
+    assert want[(1400, 1400)] == (300, 0, 0, 0)
+    assert want[(350, 1400)][0] >= 1 and want[(350, 1400)][1] >= 257 and want[(350, 1400)][2] == 0
+    pending = np.flatnonzero(need > 350)
+    assert pending.shape[0] == want[(350, 1400)][1] and (pending != np.arange(pending.shape[0])).any()
+    ix = _index(idx, x, "bf16", "ip")
+    groups = ix.group_keys(keys)
+    for depth in ((1400, 1400), (350, 1400)):
+        ix.set_group_depth(*depth)
+        _eq(ix.search_groups(q300, k, groups, g), ref, f"300 queries, lists of 1400, depth {depth}")
+        assert _stats(ix) == want[depth] and ix.group_last_stats()["longest"] == 1400, (ix.group_last_stats(), want[depth])
+    groups.close()
+    ix.close()
 
 
 # ---- 7. routes -------------------------------------------------------------------------------------------------
