@@ -558,6 +558,83 @@ int vs_group_last_stats(vs_index* index, int64_t* out, int cap);
  * search spent building the restricted set and compacting it */
 int vs_group_last_times(vs_index* index, double* out, int cap);
 
+/* ==== adjusted search ==========================================================================
+ * "Rank by the vector score mixed with a keyword score and a metadata boost": the reference fuses the
+ * vector score of its candidate_k vector hits with the keyword store's score and multiplies by a
+ * metadata boost (core/searcher.py:925-988, _compute_metadata_boost :435-449); a photo with a strong
+ * keyword hit just outside the candidate list is lost.  Per row the fused score is an affine function
+ * of the vector score, A = scale_row * S + bias_row: Elasticsearch knn + boost / function_score,
+ * Milvus's boost ranker, Qdrant's score-boosting formula; faiss has no such call.  Only the index sees
+ * the rows outside a candidate list, so only the index can rank by A exactly.
+ *
+ * The adjustment.  vs_adjust_create (dense): host fp32 scale[n] and bias[n], either may be NULL (all 1 /
+ * all 0); n must equal vs_ntotal.  vs_adjust_create_sparse: m entries (ids, scale, bias), scale / bias
+ * may be NULL alike; the ids are distinct and in [0, ntotal), in any order; every other row is plain.
+ * A row is plain iff its (scale, bias) is exactly (1.0f, +-0.0f); the others are adjusted, and
+ * vs_adjust_count returns how many there are (m_adj); vs_adjust_rows: rows covered.  scale must be
+ * finite and >= 0, bias finite: anything else, a NaN included, is VS_ERR_ARG, checked before any upload.
+ * Rows added later are no members; after vs_reset, or a vs_remove_ids that removed a row, the object is
+ * stale (the generation check of vs_sel / vs_groups).  The object is reused across searches.  Shared
+ * lock; its HBM -- fp32 scale[n] and bias[n], the ascending id list of the adjusted rows, the extrema
+ * smin, smax, bmin, bmax over the covered rows -- is counted in vs_device_bytes_live until
+ * vs_adjust_destroy. */
+typedef struct vs_adjust vs_adjust;
+int vs_adjust_create(vs_index* index, const float* scale, const float* bias, int64_t n, vs_adjust** out);
+int vs_adjust_create_sparse(vs_index* index, const int64_t* ids, const float* scale, const float* bias, int64_t m,
+                            vs_adjust** out);
+void vs_adjust_destroy(vs_adjust* adjust);
+int64_t vs_adjust_count(const vs_adjust* adjust);
+int64_t vs_adjust_rows(const vs_adjust* adjust);
+/* Members: the rows the adjustment covers, with a selector (may be NULL) those of them it allows, under
+ * the rules of vs_search_sel.
+ * Adjusted score: A = fl64(fl64((double)scale * S) + (double)bias), S the canonical fp64 score: two
+ * rounded fp64 operations, no FMA.  A plain row has A == S bit for bit.
+ * Ranking: the members by A in the metric's direction (inner product descending, L2 ascending -- for L2 a
+ * bonus is a negative bias), ties to the lower id.
+ * Outputs (host, nq x k): D = (float)A, I = the row ids, D_raw (may be NULL) = (float)S, the value
+ * vs_search reports for that row; padded as vs_search pads.
+ * With every row plain the result is bit-equal to vs_search / vs_search_sel; with a uniform (s, 0), s a
+ * power of two, the ids are those of vs_search and D is the scaled value.
+ *
+ * k < 1 or k > 3276, null q / D / I, a stale adjustment or selector and an adjustment of another index
+ * are VS_ERR_ARG before anything is launched; nq = 0 returns at once; an empty member set gives all
+ * padding.  Shared lock, one leased context, the call synchronises (the shape of vs_search_groups).
+ *
+ * Tiers (the same bits under each).  All walk the exact top-L plain lists of vs_search, rescoring every
+ * entry canonically before A is formed (A is never computed from a rounded score), L = first, then 4 L
+ * up to min(limit, members).
+ * DIRECT (AUTO takes it iff m_adj + k <= limit): one adjusted scan over the adjusted rows gives their
+ * exact top-min(k, m_adj) by A; the walk drops the list's adjusted entries and merges the plain ones with
+ * that list.  Complete iff the list held k plain entries or every member: a plain member outside the
+ * list is worse in (S, id) than k plain entries inside it, and A == S for those.  A list of k + m_adj
+ * always completes.
+ * BOUND (AUTO otherwise): no row is scanned directly.  Every member outside a list whose last entry
+ * scores S_L has S <= S_L (inner product); the rounded multiply and add are monotone and scale >= 0, so
+ * its A <= U = max(fl(fl(smax S_L) + bmax), fl(fl(smin S_L) + bmax)).  Complete iff the k-th best A of
+ * the list is strictly greater than U (L2 mirrored: S >= S_L, A >= min(fl(fl(smin S_L) + bmin),
+ * fl(fl(smax S_L) + bmin)), strictly less).  Queries open at the limit go to SCAN.
+ * SCAN: the streaming exact scan ranking by A over every member, exact for any input -- thousands of
+ * rows tied on A included (scale = 0 with a common bias is legal).
+ * Forcing DIRECT with m_adj + k > limit is VS_ERR_ARG.  Scratch is counted in vs_device_bytes_live and
+ * freed before the call returns. */
+int vs_search_adjusted(vs_index* index, const vs_adjust* adjust, const vs_sel* sel, const float* q, int64_t nq,
+                       int32_t k, float* D, int64_t* I, float* D_raw);
+#define VS_ADJUST_AUTO 0
+#define VS_ADJUST_DIRECT 1
+#define VS_ADJUST_BOUND 2
+#define VS_ADJUST_SCAN 3
+int vs_set_adjust_mode(vs_index* index, int mode);
+/* list lengths the walk is fed (tests; the same bits under every setting): first = 0 ->
+ * k + min(m_adj, max(k, 64)), limit = 0 -> vs_search's k limit; 1 <= first <= limit <= that limit */
+int vs_set_adjust_depth(vs_index* index, int32_t first, int32_t limit);
+/* last call on the handle, up to cap (7): {queries, complete after the first list, complete after a
+ * deeper list, answered by the scan, longest list walked, tier taken (VS_ADJUST_*), m_adj} */
+int vs_adjust_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/adjust_timing.py): the last call on the handle, up to cap (6): ms of
+ * HIP-event time {list search, walk} of the first list and of the deeper lists, of the direct scan over
+ * the adjusted rows and of the full scan (with the walk that reports its rows) */
+int vs_adjust_last_times(vs_index* index, double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

@@ -138,6 +138,17 @@ _SIGS = {
     "vs_set_group_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
     "vs_group_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_group_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    # adjusted search
+    "vs_adjust_create": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, ctypes.POINTER(_vp)]),
+    "vs_adjust_create_sparse": (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_i64, ctypes.POINTER(_vp)]),
+    "vs_adjust_destroy": (None, [_vp]),
+    "vs_adjust_count": (_c_i64, [_vp]),
+    "vs_adjust_rows": (_c_i64, [_vp]),
+    "vs_search_adjusted": (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_i64, ctypes.c_int32, _vp, _vp, _vp]),
+    "vs_set_adjust_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "vs_set_adjust_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
+    "vs_adjust_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_adjust_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

@@ -34,36 +34,6 @@ struct GrMembers {
     const int32_t* gsize = nullptr;  // device [G]
 };
 
-// a selector made by the call itself from a device bitmap over rows [0, n): only `bits` + `ids` are
-// read by the filtered search's road; never exported
-struct TempSel {
-    vs_sel s;
-    DevBuf bits, ids, tmp;
-    // the bitmap is in bits (ceil(n / 64) words); at most cap rows are set
-    void compact(vs_index* ix, int64_t n, int64_t cap, hipStream_t st) {
-        const size_t cnt_off = (size_t)round_up(sel_compact_groups(n) * (int64_t)sizeof(unsigned), 8);
-        tmp.ensure(cnt_off + 8);
-        ids.ensure((size_t)std::max<int64_t>(cap, 1) * sizeof(uint32_t));
-        unsigned long long* cnt_d = (unsigned long long*)((uint8_t*)tmp.p + cnt_off);
-        HIP_CHECK(launch_sel_compact(bits.as<uint64_t>(), n, tmp.as<unsigned>(), ids.as<uint32_t>(), cap, cnt_d, st));
-        unsigned long long cnt_h = 0;
-        HIP_CHECK(hipMemcpyAsync(&cnt_h, cnt_d, sizeof(cnt_h), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if ((int64_t)cnt_h > cap) throw VsError(VS_ERR_INTERNAL, "grouped search: restricted set larger than its bound");
-        s.ix = ix;
-        s.gen = ix->reset_gen.load();
-        s.device = ix->device;
-        s.n_sel = n;
-        s.m = (int64_t)cnt_h;
-        s.bits = bits.as<uint64_t>();
-        s.ids = ids.as<uint32_t>();
-    }
-    ~TempSel() {  // (the buffers free themselves; vs_sel_destroy must never see these pointers)
-        s.bits = nullptr;
-        s.ids = nullptr;
-    }
-};
-
 // where one call's answers go (found / sizes / codes always exist here; the caller's may be null)
 struct GrOut {
     int k, g;
@@ -407,11 +377,7 @@ int vs_search_groups(vs_index* ix, const vs_groups* gr, const vs_sel* sel, const
         } else {
             mb.sel = sel;
             if (!sel || sel->n_sel > gr->n_cov) {
-                const int64_t nwords = (gr->n_cov + 63) / 64;
-                cover.bits.ensure((size_t)nwords * 8);
-                if (sel) HIP_CHECK(hipMemcpyAsync(cover.bits.p, sel->bits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, st));
-                else HIP_CHECK(hipMemsetAsync(cover.bits.p, 0xFF, (size_t)nwords * 8, st));
-                cover.compact(ix, gr->n_cov, sel ? std::min(sel->m, gr->n_cov) : gr->n_cov, st);
+                cover.cover(ix, sel, gr->n_cov, st);
                 mb.sel = &cover.s;
             }
             // members of every group and the groups that have one: [gsize int32 G | cnt unsigned 2]

@@ -1,7 +1,7 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
-// vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip; the last two share
-// the list-deepening driver of vs_walk.h).
+// vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip;
+// the last three share the list-deepening driver of vs_walk.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,12 +70,12 @@ struct Ctx {
     }
 };
 
-// A walk job on the index (diversified search, grouped search): the list lengths set by the caller
+// A walk job on the index (diversified, grouped, adjusted search): the list lengths set by the caller
 // (0 = the defaults) and what the last call reported, stats[] and its HIP-event ms times[].
 struct WalkState {
     std::atomic<int> first{0}, limit{0};
     std::mutex mu;
-    int64_t stats[6] = {0, 0, 0, 0, 0, 0};
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double times[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     struct Depth { int64_t first, limit; };  // the first list's length and the longest one's
     Depth resolve(int64_t default_first, int kmax) const {
@@ -168,6 +168,12 @@ struct vs_index {
     // after a deeper list, finished by restricted rounds, restricted rounds run, longest list walked}
     // (vs_group_last_stats) and its ms {search, walk} per tier, restrict, compact (vs_group_last_times)
     vs::WalkState gr;
+    // adjusted search (vs_set_adjust_depth, vs_set_adjust_mode): the last call's {queries, complete after
+    // the first list, after a deeper list, answered by the scan, longest list walked, tier taken, adjusted
+    // rows} (vs_adjust_last_stats) and its ms {search, walk} per list tier, direct scan, full scan
+    // (vs_adjust_last_times)
+    vs::WalkState aj;
+    std::atomic<int> adjust_mode{VS_ADJUST_AUTO};
     int last_kernel_kind = 0;  // 1 = mfma, 2 = gemv, 3 = int8 mfma, 4 = int8 gemv, 5 = exact full scan
     // Screen health (first passes of MFMA batches): the certificate-failure count of a batch is read
     // back without a host wait (pinned word + event, observed by a later search).  A failed query
@@ -211,6 +217,18 @@ struct vs_groups {
     vs::DevBuf gkey;   // int64 [G] keys, ascending
     vs::DevBuf gsize;  // int32 [G] rows per group
     vs::DevBuf ukey;   // int64 [U] keys of the ungrouped rows, in row order
+};
+
+// ---- score adjustment: exact adjusted search (include/vs.h "adjusted search"; kernels: vs_adjust.hip) ----
+struct vs_adjust {
+    vs_index* ix = nullptr;
+    uint64_t gen = 0;  // the index's reset generation at creation
+    int device = 0;
+    int64_t n_cov = 0, m_adj = 0;  // rows covered, rows that are not plain
+    vs::DevBuf scale, bias;        // fp32 [n_cov]
+    vs::DevBuf ids;                // uint32 [m_adj] the adjusted rows, ascending
+    vs::DevBuf ext;                // fp32 [4] smin, smax, bmin, bmax over the covered rows (host copy below)
+    float smin = 1.0f, smax = 1.0f, bmin = 0.0f, bmax = 0.0f;
 };
 
 namespace vs {

@@ -653,6 +653,50 @@ hipError_t launch_group_restrict(const int32_t* gid, int64_t n_cov, const uint64
 // clears the bits of rows ids[0, n) (each < n_cov)
 hipError_t launch_group_clear(uint64_t* bits, int64_t n_cov, const int64_t* ids, int n, hipStream_t st);
 
+// ---- adjusted search (vs_adjust.hip) -------------------------------------------------
+// A row's adjusted score is A = fl64(fl64((double)scale[row] * S) + (double)bias[row]), S its canonical
+// fp64 score; a row with (scale, bias) = (1, +-0) is plain (A == S bit for bit).
+constexpr int AJ_THREADS = 512;           // k_adjust_walk: one workgroup per query
+constexpr int AJ_N_MAX = 2 * K_MAX;       // entries of one walk: a list and a scan list of K_MAX each
+constexpr size_t AJ_DYN_CAP = 144 * 1024; // its dynamic LDS: the entries' keys and ids, the query as fp64
+// what the adjusted scans and the walk read of a vs_adjust (and of the caller's selector)
+struct AdjustRows {
+    const float* scale;        // [n_cov]
+    const float* bias;         // [n_cov]
+    int64_t n_cov;             // rows covered: rows at or past it are no members
+    const uint64_t* sel_bits;  // the caller's selector (rows at or past n_sel are not allowed), or null
+    int64_t n_sel;
+};
+enum { AJ_PLAIN = 0, AJ_DIRECT = 1, AJ_BOUND = 2 };  // AdjustWalkArgs::mode
+struct AdjustWalkArgs {
+    const uint8_t* corpus;  // tiled shard
+    int d, dpad, dt, metric;
+    AdjustRows rows;        // (sel_bits unused: every entry is a member already)
+    const float* q;         // [nq][d] fp32 queries of the launch
+    const int64_t* I_list;  // [nq][L] each query's exact plain ranking, best first (an entry < 0 ends it), or null
+    int64_t L;
+    const int64_t* I_scan;  // [..][ks] adjusted-scan lists, best first, -1 padded; query j's is row qmap[j]; or null
+    const int64_t* qmap;    // [nq] (null: the identity)
+    int ks;
+    int mode;               // AJ_PLAIN: rank every entry, always complete; AJ_DIRECT: the list's adjusted entries
+                            // are dropped, complete iff k plain ones are left; AJ_BOUND: complete iff the k-th
+                            // best A strictly beats the bound on every row behind the list
+    double smin, smax, bmin, bmax;  // AJ_BOUND: the extrema over the covered rows
+    int k;
+    double* S_tmp;          // [nq][L + ks] scratch: the entries' canonical scores
+    int64_t* I;             // [nq][k] rows by (A, id), -1 padded
+    float* D;               // [nq][k] (float)A, padded with the worst score
+    float* D_raw;           // [nq][k] (float)S, padded alike
+    int32_t* complete;      // [nq] (a list shorter than L held every member: complete)
+};
+size_t adjust_walk_lds(int64_t n_entries, int d);  // dynamic LDS of one walk workgroup
+hipError_t launch_adjust_walk(const AdjustWalkArgs& a, int nq, hipStream_t st);
+// fs_scan_body ranking by A: ids null = rows [0, a.n_valid) (the caller sets n_valid = rows.n_cov), else
+// the m listed rows (ascending; those at or past rows.n_cov, or not allowed by rows.sel_bits, are passed
+// over); a.G, qy, a.cert / a.all_queries as in launch_sel_scan.  D / S64 report A.
+hipError_t launch_adjust_scan(const FullScanArgs& a, const AdjustRows& rows, const uint32_t* ids, int64_t m, int qy,
+                              hipStream_t st);
+
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
 // int8 screen copy of stored rows [r0, r0 + n) (maxes[0..1]: running max ||x_hat||, max beta)

@@ -1,5 +1,6 @@
 // vs_scan.h -- the streaming exact scan shared by k_full_scan (vs_fullscan.hip: every row of the
-// shard) and k_sel_scan (vs_selscan.hip: the rows of a selector's ascending id list): the bounded
+// shard), k_sel_scan (vs_selscan.hip: the rows of a selector's ascending id list) and k_adjust_scan
+// (vs_adjust.hip: either sequence, ranked by a per-row affine function of the score): the bounded
 // running top-k under the total order (score, then id), its batch sort / rank merge, and the last
 // workgroup's merge of the per-workgroup lists (st_agent / ld_agent hand-off).
 //
@@ -106,9 +107,15 @@ inline size_t fs_lds_bytes(int k, int d, int* KL_out, bool* qlds_out) {
 // sel_ids[0, sel_m) (ascending, each < a.n_valid), and the grid's y dimension deals the queries
 // (slice y takes queries y, y + gridDim.y, ...: a short list fills few workgroups per query, and a
 // query's lists, counter and outputs are its own).
-template <int DT, int METRIC, bool QLDS, bool SEL>
+// XF: what a row's canonical score becomes before the running top-k.  FsPlain ranks by the score itself
+// and compiles to nothing; an active transform (vs_adjust.hip) may pass a row over, or put another key
+// in the score's place -- the key is what the lists hold and what D / S64 report.
+struct FsPlain {
+    static constexpr bool active = false;
+};
+template <int DT, int METRIC, bool QLDS, bool SEL, class XF = FsPlain>
 __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, const uint32_t* __restrict__ sel_ids,
-                                             int64_t sel_m) {
+                                             int64_t sel_m, const XF& xf = XF()) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     if (a.gate && *a.gate == 0) return;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -160,8 +167,10 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
 #pragma unroll
                     for (int i = 0; i < RR; ++i) {
                         if (rr[i] < 0) continue;
-                        const double s = METRIC == METRIC_L2 ? -s4[i] : s4[i];
+                        double s = METRIC == METRIC_L2 ? -s4[i] : s4[i];
                         const uint32_t id = (uint32_t)rr[i];
+                        if constexpr (XF::active)
+                            if (!xf.template key<METRIC>(id, s4[i], s)) continue;
                         if (!full || fs_better(s, id, ts, ti)) {
                             const int slot = atomicAdd(&nb_s, 1);
                             L.bsc[slot] = s;

@@ -33,6 +33,45 @@ struct WalkTimes {
     double& walk(int tier) { return ms[2 * tier + 1]; }
 };
 
+// a selector made by a call itself from a device bitmap over rows [0, n): only `bits` + `ids` are
+// read by the filtered search's road; never exported
+struct TempSel {
+    vs_sel s;
+    DevBuf bits, ids, tmp;
+    // the bitmap is in bits (ceil(n / 64) words); at most cap rows are set
+    void compact(vs_index* ix, int64_t n, int64_t cap, hipStream_t st) {
+        const size_t cnt_off = (size_t)round_up(sel_compact_groups(n) * (int64_t)sizeof(unsigned), 8);
+        tmp.ensure(cnt_off + 8);
+        ids.ensure((size_t)std::max<int64_t>(cap, 1) * sizeof(uint32_t));
+        unsigned long long* cnt_d = (unsigned long long*)((uint8_t*)tmp.p + cnt_off);
+        HIP_CHECK(launch_sel_compact(bits.as<uint64_t>(), n, tmp.as<unsigned>(), ids.as<uint32_t>(), cap, cnt_d, st));
+        unsigned long long cnt_h = 0;
+        HIP_CHECK(hipMemcpyAsync(&cnt_h, cnt_d, sizeof(cnt_h), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        if ((int64_t)cnt_h > cap) throw VsError(VS_ERR_INTERNAL, "walk: a compacted member set larger than its bound");
+        s.ix = ix;
+        s.gen = ix->reset_gen.load();
+        s.device = ix->device;
+        s.n_sel = n;
+        s.m = (int64_t)cnt_h;
+        s.bits = bits.as<uint64_t>();
+        s.ids = ids.as<uint32_t>();
+    }
+    // the rows of [0, n_cov) that sel allows (null: all of them), for an object that covers fewer rows
+    // than the selector or the index does
+    void cover(vs_index* ix, const vs_sel* sel, int64_t n_cov, hipStream_t st) {
+        const int64_t nwords = (n_cov + 63) / 64;
+        bits.ensure((size_t)nwords * 8);
+        if (sel) HIP_CHECK(hipMemcpyAsync(bits.p, sel->bits, (size_t)nwords * 8, hipMemcpyDeviceToDevice, st));
+        else HIP_CHECK(hipMemsetAsync(bits.p, 0xFF, (size_t)nwords * 8, st));
+        compact(ix, n_cov, sel ? std::min(sel->m, n_cov) : n_cov, st);
+    }
+    ~TempSel() {  // (the buffers free themselves; vs_sel_destroy must never see these pointers)
+        s.bits = nullptr;
+        s.ids = nullptr;
+    }
+};
+
 struct Deepened {
     std::vector<int64_t> pending;  // the queries no list completed, ascending
     int64_t done[2] = {0, 0};      // queries complete after the first list, after a deeper one

@@ -375,6 +375,74 @@ class Groups:
             pass
 
 
+ADJUST_MODES = {"auto": 0, "direct": 1, "bound": 2, "scan": 3}  # VS_ADJUST_*
+
+
+def adjust_arrays(n: int, scale=None, bias=None):
+    """Dense ``(scale, bias)`` of an adjustment over ``n`` rows as contiguous float32 arrays (``None``
+    stays ``None``: all 1 / all 0); a wrong length is ``ValueError``.  Values are checked by the library
+    (``scale`` finite and ``>= 0``, ``bias`` finite)."""
+    out = []
+    for name, a in (("scale", scale), ("bias", bias)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (int(n),):
+                raise ValueError(f"{name} must be {int(n)} numbers (one per row), got shape {a.shape}")
+        out.append(a)
+    return out[0], out[1]
+
+
+def adjust_sparse_arrays(ids, scale=None, bias=None):
+    """``(ids int64, scale, bias)`` of a sparse adjustment, one entry per listed row."""
+    ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+    scale, bias = adjust_arrays(ids.shape[0], scale, bias)
+    return ids, scale, bias
+
+
+class Adjust:
+    """A per-row score adjustment of one :class:`FlatIndex` (``vs_adjust``, include/vs.h): row ``i`` ranks
+    by ``A = scale[i] * S + bias[i]`` instead of its score ``S``.  Uploaded once and reused across
+    searches; it covers the rows present when it was made (rows added later are no members of an adjusted
+    search) and is stale after ``reset()`` or a ``remove_ids`` that removed a row."""
+
+    def __init__(self, index: "FlatIndex", scale=None, bias=None, ids=None) -> None:
+        self._h = None
+        self._index = index  # (keeps the index alive while the adjustment is)
+        self._L = index._L
+        h = ctypes.c_void_p()
+        if ids is None:
+            scale, bias = adjust_arrays(index.ntotal, scale, bias)
+            check(self._L.vs_adjust_create(index._h, None if scale is None else _ptr(scale),
+                                           None if bias is None else _ptr(bias), index.ntotal, ctypes.byref(h)))
+        else:
+            ids, scale, bias = adjust_sparse_arrays(ids, scale, bias)
+            check(self._L.vs_adjust_create_sparse(index._h, _ptr(ids) if ids.size else None,
+                                                  None if scale is None else _ptr(scale),
+                                                  None if bias is None else _ptr(bias), ids.shape[0], ctypes.byref(h)))
+        self._h = h
+
+    @property
+    def count(self) -> int:
+        """Adjusted rows: those whose ``(scale, bias)`` is not exactly ``(1, 0)``."""
+        return int(self._L.vs_adjust_count(self._h))
+
+    @property
+    def rows(self) -> int:
+        """Rows covered."""
+        return int(self._L.vs_adjust_rows(self._h))
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            self._L.vs_adjust_destroy(self._h)
+        self._h = None
+
+    def __del__(self) -> None:  # pragma: no cover - interpreter shutdown ordering
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class FlatIndex:
     """Exact flat inner-product / squared-L2 index resident in one GPU's HBM."""
 
@@ -655,6 +723,68 @@ class FlatIndex:
         return {"search_ms": [float(buf[0]), float(buf[2]), float(buf[4])],
                 "walk_ms": [float(buf[1]), float(buf[3]), float(buf[5])],
                 "restrict_ms": float(buf[6]), "compact_ms": float(buf[7])}
+
+    def score_adjust(self, scale=None, bias=None) -> Adjust:
+        """Reusable :class:`Adjust` over the rows present now: ``ntotal`` scales and biases, one per row
+        (``None``: all 1 / all 0)."""
+        return Adjust(self, scale, bias)
+
+    def score_adjust_sparse(self, ids, scale=None, bias=None) -> Adjust:
+        """Reusable :class:`Adjust` that adjusts the listed rows (distinct ids, any order) and leaves every
+        other row plain."""
+        return Adjust(self, scale, bias, ids=ids)
+
+    def search_adjusted(self, q, k: int, adjust: Adjust, sel=None, return_raw: bool = False):
+        """Exact top-``k`` by the adjusted score ``A = scale * S + bias`` (``vs_search_adjusted``,
+        include/vs.h): the members -- the rows ``adjust`` covers, under ``sel`` those of them it allows --
+        ranked by ``A`` in the metric's direction, ties to the lower id.  Returns ``(D, I)`` with ``D`` the
+        adjusted scores, and with ``return_raw`` ``(D, I, D_raw)``, ``D_raw`` the scores :meth:`search`
+        reports for the same rows."""
+        q = self._queries(q, "search_adjusted")
+        if not isinstance(adjust, Adjust):
+            raise TypeError("adjust must be an Adjust object (FlatIndex.score_adjust)")
+        nq, k = q.shape[0], int(k)
+        if k < 1:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "k must be >= 1")
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        R = np.empty((nq, k), dtype=np.float32) if return_raw else None
+        with self._sel(sel) as (_, sh):
+            if adjust._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "adjustment is closed")
+            check(self._L.vs_search_adjusted(self._h, adjust._h, sh, _ptr(q), nq, k, _ptr(D), _ptr(I),
+                                             _ptr(R) if return_raw else None))
+        return (D, I, R) if return_raw else (D, I)
+
+    def set_adjust_mode(self, mode: str) -> None:
+        """Force the tier of adjusted searches (``"direct"``, ``"bound"``, ``"scan"``) or let the library
+        choose (``"auto"``); the same bits under every mode (``vs_set_adjust_mode``)."""
+        if mode not in ADJUST_MODES:
+            raise ValueError(f"adjust mode must be one of {sorted(ADJUST_MODES)}")
+        check(self._L.vs_set_adjust_mode(self._h, ADJUST_MODES[mode]))
+
+    def set_adjust_depth(self, first: int = 0, limit: int = 0) -> None:
+        """The list lengths :meth:`search_adjusted` walks: the first list and the longest one (``0`` = the
+        defaults; the same bits under every setting, ``vs_set_adjust_depth``)."""
+        check(self._L.vs_set_adjust_depth(self._h, int(first), int(limit)))
+
+    def adjust_last_stats(self) -> dict:
+        """The last :meth:`search_adjusted`: queries, how many were complete after the first list, after a
+        deeper list, how many the scan answered, the longest list walked, the tier taken and the adjusted
+        rows (``vs_adjust_last_stats``)."""
+        buf = (ctypes.c_int64 * 7)()
+        check(self._L.vs_adjust_last_stats(self._h, buf, 7))
+        tier = {v: n for n, v in ADJUST_MODES.items()}[int(buf[5])]
+        return {"queries": int(buf[0]), "first": int(buf[1]), "deeper": int(buf[2]), "scan": int(buf[3]),
+                "longest": int(buf[4]), "tier": tier, "adjusted": int(buf[6])}
+
+    def adjust_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`search_adjusted`: list search and walk per list tier,
+        the direct scan over the adjusted rows and the full scan (``vs_adjust_last_times``)."""
+        buf = (ctypes.c_double * 6)()
+        check(self._L.vs_adjust_last_times(self._h, buf, 6))
+        return {"search_ms": [float(buf[0]), float(buf[2])], "walk_ms": [float(buf[1]), float(buf[3])],
+                "direct_scan_ms": float(buf[4]), "full_scan_ms": float(buf[5])}
 
     def set_range_mode(self, mode: str) -> None:
         """Force the tier of range searches (``"scan"``, ``"screen"`` where it applies) or let the

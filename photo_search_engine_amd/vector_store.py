@@ -34,6 +34,7 @@ int8 -- the certified int8 pre-screen, same exact results, see INTEGRATION.md §
 from __future__ import annotations
 
 import json
+import math
 import os
 import struct
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -104,6 +105,17 @@ def _merge_topk(D1: np.ndarray, I1: np.ndarray, D2: np.ndarray, I2: np.ndarray, 
         Io = np.concatenate([Io, np.full((Io.shape[0], pad), -1, dtype=Io.dtype)], axis=1)
     Do = np.where(Io >= 0, Do, np.float32(-np.finfo(np.float32).max if higher_is_better else np.finfo(np.float32).max))
     return Do.astype(np.float32), Io.astype(np.int64)
+
+
+def hybrid_adjustment(keyword_score: Optional[float], boost: float, vector_weight: float,
+                      keyword_weight: float) -> Tuple[float, float]:
+    """``(scale, bias)`` of one item of :meth:`VectorStore.search_hybrid`, in cosine units: with a
+    keyword hit ``A = b (wv D + wk (2 ks - 1)) + (b - 1)``, without ``A = b D + (b - 1)``; ``(1, 0)``
+    for an item with no hit and ``b = 1``.  Python floats (the index rounds them to fp32)."""
+    b = float(boost)
+    if keyword_score is None:
+        return b, b - 1.0
+    return b * vector_weight, b * keyword_weight * (2.0 * float(keyword_score) - 1.0) + (b - 1.0)
 
 
 def _hnsw_graph_search() -> bool:
@@ -386,6 +398,78 @@ class VectorStore:
                      for distance, index in zip(res.D[0, slot, :found].tolist(), res.I[0, slot, :found].tolist())]
             out.append({"group": (key if values is None else values[key]) if key >= 0 else None, "size": int(res.sizes[0, slot]), "items": items})
         return out
+
+    def search_hybrid(self, query_embedding: List[float], top_k: int, keyword_scores: Dict[str, float],
+                      vector_weight: float = 0.8, keyword_weight: float = 0.2, boosts=None, allowed=None) -> List[Dict]:
+        """:meth:`search` ranked by the fused score of the reference's hybrid search (an addition at the
+        boundary; Elasticsearch ``knn`` + ``boost`` / ``function_score``, Milvus's boost ranker, Qdrant's
+        score-boosting formula): the vector score mixed with the keyword store's score for the photos
+        that store returned, times a metadata boost (core/searcher.py:925-988, ``_compute_metadata_boost``
+        :435-449).  The reference fuses only its ``candidate_k`` vector hits, so a photo with a strong
+        keyword hit or a boost just outside them is lost, or enters at ``x 0.65`` with no vector score;
+        here every item is ranked by its fused score, exactly.
+
+        Cosine stores only (``ValueError`` on an L2 store: the reference's L2 map is an exponential, not
+        affine).  In cosine units, with ``D`` the cosine, ``ks`` an item's keyword score and ``b`` its
+        boost: ``A = b (wv D + wk (2 ks - 1)) + (b - 1)`` with a keyword hit, ``A = b D + (b - 1)``
+        without; an item with no hit and ``b = 1`` keeps ``A = D``, so a typical query adjusts only the
+        keyword store's hits and the boosted items.  Each result is ``{"metadata", "score": (A + 1) / 2,
+        "vector_score": (D + 1) / 2, "keyword_score": ks or None}``.  This is the linear part of the
+        reference's ``_distance_to_score``: its stretch above 0.7 and its rounding are not reproduced.
+
+        ``keyword_scores``: ``{photo_path: score}``; paths the store does not hold are ignored, as the
+        reference ignores keyword hits absent from the local index (:943-946).  ``boosts``: ``{photo_path:
+        factor}`` or a callable ``metadata -> factor`` (``None`` = 1).  Weights and factors must be finite
+        and ``>= 0``.  The guards, the normalisation and the ``k = min(top_k, ntotal)`` clamp are
+        :meth:`search`'s; ``allowed`` as there."""
+        if self.metric != "cosine":
+            raise ValueError("search_hybrid needs a cosine store (the L2 score map is not affine)")
+        wv, wk = float(vector_weight), float(keyword_weight)
+        if not (math.isfinite(wv) and math.isfinite(wk) and wv >= 0 and wk >= 0):
+            raise ValueError("vector_weight and keyword_weight must be finite and >= 0")
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        if len(query_embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
+        if not hasattr(self.index, "score_adjust_sparse"):
+            raise NotImplementedError("search_hybrid needs a one-device flat index")
+        n = int(self.index.ntotal)
+        k = min(int(top_k), n)
+        if k < 1:
+            raise ValueError("top_k must be >= 1")
+        hits: Dict[int, float] = {}
+        for path, ks in (keyword_scores or {}).items():
+            row = self._path_to_index.get(path)
+            if row is not None and row < n:
+                hits[row] = float(ks)
+        factor: Dict[int, float] = {}
+        if callable(boosts):
+            for row, metadata in enumerate(self.metadata[:n]):
+                b = boosts(metadata)
+                if b is not None and float(b) != 1.0:
+                    factor[row] = float(b)
+        elif boosts:
+            for path, b in boosts.items():
+                row = self._path_to_index.get(path)
+                if row is not None and row < n and float(b) != 1.0:
+                    factor[row] = float(b)
+        rows = sorted(set(hits) | set(factor))
+        scale = np.empty((len(rows),), dtype=np.float32)
+        bias = np.empty((len(rows),), dtype=np.float32)
+        for j, row in enumerate(rows):
+            scale[j], bias[j] = hybrid_adjustment(hits.get(row), factor.get(row, 1.0), wv, wk)
+        if not (np.all(np.isfinite(scale)) and np.all(np.isfinite(bias)) and np.all(scale >= 0)):
+            raise ValueError("keyword scores must be finite, boosts finite and >= 0")
+        adjust = self.index.score_adjust_sparse(np.asarray(rows, dtype=np.int64), scale, bias)
+        try:
+            sel = None if allowed is None else self._allowed_rows(allowed)
+            A, I, D = self.index.search_adjusted(self._normalize_query(query_embedding), k, adjust, sel=sel,
+                                                 return_raw=True)
+        finally:
+            adjust.close()
+        return [{"metadata": self.metadata[index], "score": (float(a) + 1.0) / 2.0,
+                 "vector_score": (float(d) + 1.0) / 2.0, "keyword_score": hits.get(index)}
+                for a, index, d in zip(A[0].tolist(), I[0].tolist(), D[0].tolist()) if index != -1]
 
     def _group_keys(self, group_by, n: int):
         """``(groups, values, own)`` of a ``group_by``: the index's group keys object, the value each
