@@ -212,6 +212,11 @@ int vs_screen_probe(vs_index* index, const float* q_dev, int64_t nq, int32_t scr
  * survivors and results under either schedule. */
 int vs_set_k1_schedule(int32_t schedule);
 int vs_k1_schedule(void);
+/* The int8 screen's query credit, process-wide: 1 (default) = a query whose own int8 rounding error is
+ * below the share every row's bound carries for it gets the difference back, so its exact refine
+ * scores fewer rows; 0 = no credit.  Both margins are proven: the same results under either. */
+int vs_set_i8_query_credit(int32_t on);
+int vs_i8_query_credit(void);
 enum {
     VS_K1P_LOADS = 0,        /* corpus loads + query LDS-DMAs + the per-K-step barriers */
     VS_K1P_LDS = 1,          /* + the query-fragment LDS reads */
@@ -229,6 +234,9 @@ int64_t vs_uncertified_count(vs_index* index);   /* first-pass certificate failu
 /* queries answered by the exact full scan (no bounded screen could certify them; see
  * vs_search_device_exact); synchronises */
 int64_t vs_full_scan_count(vs_index* index);
+/* stored rows the adaptive exact refine (behind the int8 screen and the native MFMA first passes) has
+ * scored so far, over all queries; synchronises */
+int64_t vs_refine_rows_count(vs_index* index);
 /* pinned host bytes the index holds for vs_search's query / result staging (all contexts); each
  * context stages at most 8 MiB and loops over query chunks beyond that */
 int64_t vs_host_staging_bytes(vs_index* index);

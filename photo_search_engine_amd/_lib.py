@@ -92,6 +92,9 @@ _SIGS = {
                                    _vp, _vp, _vp, _vp]),
     "vs_set_k1_schedule": (ctypes.c_int, [ctypes.c_int32]),
     "vs_k1_schedule": (ctypes.c_int, []),
+    "vs_set_i8_query_credit": (ctypes.c_int, [ctypes.c_int32]),
+    "vs_i8_query_credit": (ctypes.c_int, []),
+    "vs_refine_rows_count": (_c_i64, [_vp]),
     "vs_host_staging_bytes": (_c_i64, [_vp]),
     "vs_device_bytes_live": (_c_i64, []),
     "vs_screen_copy_bytes": (_c_i64, [_vp]),

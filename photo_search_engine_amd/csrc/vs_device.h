@@ -442,6 +442,16 @@ __device__ __forceinline__ float f32_up(double v) {  // smallest fp32 >= v (v >=
     if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);
     return f;
 }
+__device__ __forceinline__ float f32_down(double v) {  // largest fp32 <= v (v >= 0, finite)
+    float f = (float)v;
+    if ((double)f > v) f = __uint_as_float(__float_as_uint(f) - 1u);  // (f > v >= 0: f > 0)
+    return f;
+}
+__device__ __forceinline__ float f32_ceil(double v) {  // smallest fp32 >= v, either sign (finite)
+    float f = (float)v;
+    if ((double)f < v) f = nextafterf(f, INFINITY);
+    return f;
+}
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);

@@ -122,7 +122,8 @@ struct vs_index {
     unsigned* d_unres = nullptr;  // queries answered by the exact full scan (no bounded screen certified them)
     float maxsq = 0.0f;
     // int8 screen copy (VS_SCREEN_I8): codes in row tiles of 64-element chunks + per-row scale and
-    // error norm; d_maxsq[2..3] = max ||x_hat||, max error norm (fp32 bits, certificate margins)
+    // error norm; d_maxsq[2..3] = max ||x_hat||, max error norm (fp32 bits, certificate margins);
+    // d_maxsq[8] = min ||x_hat|| (the query credit); every word: vs_internal.h IX_WORDS
     int screen = VS_SCREEN_NATIVE;
     int dpad8 = 0;
     int64_t cap8 = 0;
@@ -245,6 +246,7 @@ void release_ctx(vs_index* ix, Ctx* c);
 // device maxima (synchronises the ingest stream).
 void quantize_rows(vs_index* ix, int64_t r0, int64_t n, hipStream_t st);
 void refresh_maxsq(vs_index* ix);
+void reset_i8_stats(vs_index* ix, hipStream_t st);  // maxima 0, min ||s c|| +inf: before a re-quantisation of every row
 
 // A leased context works on `st` (null = the context's own stream): the lease first orders `st`
 // behind the previous lease's work, and on release records the context's idle event on `st`.

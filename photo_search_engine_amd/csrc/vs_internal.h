@@ -375,6 +375,8 @@ struct RefineArgs {
     unsigned* uncert;      // device counter (may be null)
     int optimistic;        // screened with an optimistic seed: fewer than Kp candidates = uncertified
     const float* qeps;     // int8 screen (k_refine_wide): per query, true score <= key_score + qeps
+                           //  (negative where the query's int8 error earns a credit, k_pack_qtile_i8)
+    unsigned long long* rows;  // k_refine_wide: device count of the rows it scores (or null)
     const u64* drop;       // MFMA: per query, the workgroups' largest compaction threshold (or null)
     const u64* thr0;       // the screen's starting threshold per query (or null = none)
     const unsigned* i8max; // int8 GEMV screen: (max ||x_hat||, max beta) fp32 bits -> the certificate margin
@@ -699,7 +701,21 @@ hipError_t launch_adjust_scan(const FullScanArgs& a, const AdjustRows& rows, con
 
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
-// int8 screen copy of stored rows [r0, r0 + n) (maxes[0..1]: running max ||x_hat||, max beta)
+// The index's device words (vs_index::d_maxsq): [0] max ||x||^2, [1] uncertified counter, [2..3] int8
+// screen maxima (max ||s c||, max beta; fp32 bits), [4] full-scan counter, [5..6] group residuals
+// (max ||mu_g||, groups with a mean), [7] max ||x - s c||, [8] min ||s c|| over the quantised rows
+// (fp32 bits, rounded down; +inf while no row is quantised), [9] spare, [10..11] one 64-bit count of
+// the rows k_refine_wide scored (vs_refine_rows_count).  The int8 kernels get `maxes` = words 2 on.
+constexpr int IX_WORDS = 12;
+constexpr int IX_REFINE_ROWS = 10;  // (8-byte aligned)
+constexpr int I8_MIN_XH = 6;        // maxes[I8_MIN_XH] = word 8
+constexpr unsigned F32_INF_BITS = 0x7F800000u;
+// the int8 query credit (vs_set_i8_query_credit): a query whose own int8 error is below the share the
+// rows' bound words carry for it gets the difference back in its refine margin (k_pack_qtile_i8)
+void set_i8_query_credit(int on);
+int i8_query_credit();
+// int8 screen copy of stored rows [r0, r0 + n) (maxes[0..1]: running max ||x_hat||, max beta;
+// maxes[I8_MIN_XH]: running min ||x_hat||)
 hipError_t launch_quant_rows(int dt, const uint8_t* data, int dpad, int64_t r0, int64_t n, int d, uint8_t* data8,
                              int dpad8, uint32_t* rsb, unsigned* maxes, hipStream_t st, const uint16_t* gmean = nullptr);
 // group means of the int8 copy (groups [g0, g0 + ng) of I8_GROUP_ROWS rows, rows < n_rows; bf16

@@ -284,7 +284,8 @@ __global__ void __launch_bounds__(256) k_pack_qtile_split(const float* __restric
 // i8_eps_q); (s, beta) packed in one u32 per row (the screen
 // epilogue reads 4 B per row).  Also the running maxima of ||s c|| and beta
 // (maxes[0], maxes[1], fp32 bits) that bound the query-side and rounding terms of the refine's
-// certificate.  The codes need not be the nearest: whatever rint gives, beta is measured.
+// certificate, and the running minimum of ||s c|| (maxes[I8_MIN_XH]) behind the query credit.
+// The codes need not be the nearest: whatever rint gives, beta is measured.
 // Layout: row tiles of TR rows, 64-element chunks, [chunk][row][64 B] -- one 16 KiB block per
 // MFMA K-step, the same block geometry as the bf16 layout.
 // ------------------------------------------------------------------------------------------------
@@ -371,7 +372,8 @@ __global__ void __launch_bounds__(256) k_group_means(const uint8_t* __restrict__
 // word carries beta_x = ||x - s_x c_x|| + eps_q ||s_x c_x||, eps_q the typical relative int8 error of
 // a d-vector (rms t / sqrt(12) per element, t = max / 127 ~ sqrt(2 ln 2d) sigma / 127), +10%; a
 // query whose own error exceeds eps_q ||q|| pays the excess x max ||s_x c_x|| in its margin
-// (k_pack_qtile_i8).  So a row far from its group mean widens only its own key, not every query's
+// (k_pack_qtile_i8), and one whose error falls short of it gets the deficit x min ||s_x c_x|| back
+// (the query credit).  So a row far from its group mean widens only its own key, not every query's
 // margin (cluster-boundary rows of group residuals: ||s_x c_x|| up to ~1.4 ||x||).
 __host__ __device__ inline double i8_eps_q(int d) {
     return 1.1 * sqrt(2.0 * log(2.0 * (double)(d > 1 ? d : 1))) / (127.0 * 3.4641016151377544);
@@ -425,9 +427,21 @@ __global__ void __launch_bounds__(256) k_quant_rows(const uint8_t* __restrict__ 
         const uint32_t bbits = bf16_bits_up(f32_up((sqrt(e2) + i8_eps_q(d) * xh) * (1.0 + 1e-9) +
                                                    (mu ? sqrt(r2) * 4.440892098500626e-16 : 0.0)));
         rsb[row] = sbits | (bbits << 16);
-        atomicMax(&maxes[0], __float_as_uint(f32_up(sqrt(c2) * (double)sc * (1.0 + 1e-9))));
-        atomicMax(&maxes[1], bbits << 16);  // the fp32 bits of the bf16 bound
-        atomicMax(&maxes[5], __float_as_uint(f32_up(sqrt(e2) * (1.0 + 1e-9))));  // max ||x - s c|| (GEMV depth)
+        // The running extrema, one word each for every row of the index: an atomic only where the
+        // row would move the word.  The words are monotone, so a value the (possibly stale) load
+        // already covers is covered by the word itself.  (One atomic per row and word serialised on
+        // the word's address: 0.36 s for the copy of 10M x 1536 rows against 0.07 s this way,
+        // profiles/ab_cfg3_query_credit.txt.)
+        auto raise = [&](int i, unsigned v) {
+            if (v > __atomic_load_n(&maxes[i], __ATOMIC_RELAXED)) atomicMax(&maxes[i], v);
+        };
+        raise(0, __float_as_uint(f32_up(xh * (1.0 + 1e-9))));
+        raise(1, bbits << 16);  // the fp32 bits of the bf16 bound
+        raise(5, __float_as_uint(f32_up(sqrt(e2) * (1.0 + 1e-9))));  // max ||x - s c|| (GEMV depth)
+        // min ||s c|| (fp32 bits, rounded down; non-negative floats order as their bits): the row
+        // factor of the credit a query of small int8 error gets back (k_pack_qtile_i8)
+        const unsigned lo = __float_as_uint(f32_down(xh * (1.0 - 1e-9)));
+        if (lo < __atomic_load_n(&maxes[I8_MIN_XH], __ATOMIC_RELAXED)) atomicMin(&maxes[I8_MIN_XH], lo);
     }
 }
 
@@ -486,7 +500,12 @@ __global__ void __launch_bounds__(256) k_group_dots(const uint16_t* __restrict__
 // one wave per query.  qfac = (t_q, ||q|| rounded up / t_q); qeps = the query-side margin of the
 // screen key (key = s_x t_q <c_x, c_q> + beta_x ||q||, see k_screen_mfma):
 //   true <x, q> <= s_x t_q <c_x, c_q> + ||x - s_x c_x|| ||q|| + ||s_x c_x|| ||q - t_q c_q|| + rounding
-//               <= key + max ||s_x c_x|| max(0, ||q - t_q c_q|| - eps_q ||q||) + rounding <= key_score + qeps.
+//               =  key + ||s_x c_x|| (||q - t_q c_q|| - eps_q ||q||) + rounding.
+// The bracket is the query's own: where its error exceeds the share eps_q ||q|| the rows carry, every
+// row is covered by max ||s_x c_x|| x the excess; where it falls short of it (the usual case: a
+// Gaussian query's error is ~0.8 eps_q ||q||), every key overstates by at least min ||s_x c_x|| x the
+// deficit, and qeps takes that credit -- it may be negative (credit != 0; vs_set_i8_query_credit).
+// Either way true <= key_score + qeps.  A zero query has no error and no norm: no credit.
 // Also zeroes the survivor-list lengths and the workgroup drop bounds of the screen that follows.
 // NDT (bf16 / f16; 0 = none): also the device fallback round's native tile (NativeTile, the layout
 // and qinfo of k_pack_qtile<NDT>), from the same loaded values -- the round's gated pack launch
@@ -497,7 +516,7 @@ __global__ void __launch_bounds__(256) k_pack_qtile_i8(const float* __restrict__
                                                         float* __restrict__ qeps, const unsigned* __restrict__ maxes,
                                                         int* __restrict__ gcnt, u64* __restrict__ drop,
                                                         int* __restrict__ fails, const unsigned* __restrict__ l2max,
-                                                        float gamma, NativeTile nat) {
+                                                        float gamma, NativeTile nat, int credit) {
     // one workgroup per query (256 threads over its d elements; a query's pack is a chain of
     // reductions, so 4x the waves per query shorten the launch)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -610,8 +629,15 @@ __global__ void __launch_bounds__(256) k_pack_qtile_i8(const float* __restrict__
         qfac[r] = make_float2(t, t > 0.0f ? qn / t : 0.0f);
         // the rows' bound words cover eps_q ||q|| of this query's error (k_quant_rows); the excess
         // over it, times the largest ||s_x c_x||
-        const double excess = fmax(0.0, eq - i8_eps_q(d) * sqrt(n2) * (1.0 - 1e-9));
+        // (eq is rounded up and the share down: `over` is an upper bound of the true difference, so
+        // the excess is never too small and the deficit never too large)
+        const double over = eq - i8_eps_q(d) * sqrt(n2) * (1.0 - 1e-9);
+        const double excess = fmax(0.0, over);
         double e = X * excess + slop;
+        // the credit: min ||s_x c_x|| (stored rounded down) x the deficit, scaled down -- every
+        // rounding of the part that is subtracted goes toward a smaller credit
+        const double Xmin = (double)__uint_as_float(maxes[I8_MIN_XH]);
+        double cr = (credit && t > 0.0f && over < 0.0 && Xmin < (double)INFINITY) ? Xmin * -over * (1.0 - 1e-9) : 0.0;
         if (l2max) {
             // L2 keys fl(2 fl(t v) - ||x||^2_fp32) bound 2 <x, q> - ||x||^2: twice the inner-product
             // margin, the fp32 norm's error (gamma_d ||x||^2, its canonical sum) and the key's last
@@ -620,8 +646,11 @@ __global__ void __launch_bounds__(256) k_pack_qtile_i8(const float* __restrict__
             e = 2.0 * e + ((double)gamma + 2.0 * 5.9604644775390625e-08) * S +
                 2.0 * 5.9604644775390625e-08 * (X * qh + B * (double)qn);
             e *= 1.01;
+            cr *= 2.0;  // (the inner-product part is doubled, its credit with it; exact)
         }
-        qeps[r] = f32_up((e) * (1.0 + 1e-9));
+        // e >= 1e-30 is scaled up, the credit was scaled down; their fp64 difference rounds by 2^-53
+        // of itself, far inside those 1e-9; the fp32 result is rounded toward +inf
+        qeps[r] = f32_ceil(e * (1.0 + 1e-9) - cr);
     }
 }
 
@@ -661,6 +690,13 @@ namespace vs {
 static std::atomic<int> g_k1_sched{1};
 void set_k1_schedule(int s) { g_k1_sched.store(s); }
 int k1_schedule() { return g_k1_sched.load(std::memory_order_relaxed); }
+
+// the int8 query credit (vs_set_i8_query_credit; k_pack_qtile_i8): 1 = a query whose int8 error is
+// below the rows' share for it narrows its refine window by the difference; 0 = no credit (the margin
+// before it, for the in-process A/B).  Results are identical: both margins are proven.
+static std::atomic<int> g_i8_credit{1};
+void set_i8_query_credit(int on) { g_i8_credit.store(on ? 1 : 0); }
+int i8_query_credit() { return g_i8_credit.load(std::memory_order_relaxed); }
 
 bool i8_direct_ok(int dpad8) { return dpad8 % (64 * I8D_U) == 0 && dpad8 >= 2 * 64 * I8D_U; }
 bool d16_direct_ok(int dpad) { return dpad % (CH * I8D_U) == 0 && dpad >= 2 * CH * I8D_U; }
@@ -1478,13 +1514,16 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_redo(RefineArgs a, int KP
 
 // ------------------------------------------------------------------------------------------------
 // K5w: exact refine behind the int8 screen and the native MFMA screen's first passes (inner
-// product) -- adaptive depth, two phases, one block per query.  The screen keys are within qeps of
-// the true score from above: int8 keys are upper bounds, true <x, q> <= key_score + qeps[q]
-// (k_pack_qtile_i8); native keys are within the native margin either way.
+// product) -- adaptive depth, two phases, one block per query.  The screen keys bound the true score
+// from above up to qeps: int8 keys have true <x, q> <= key_score + qeps[q] (k_pack_qtile_i8), and
+// qeps[q] is negative for a query whose own int8 error is below the share the rows' bounds carry
+// (every key then overstates by at least -qeps); native keys are within the native margin either way.
 //  A: the best KA keys of the query's survivor list are scored exactly (canonical fp64); T' = the
 //     k-th best of them is a lower bound of the final k-th best exact score T.
 //  B: every other key with key_score >= T' - qeps could still reach T': those rows are scored too.
-//     Every survivor left unscored has true < T' <= T.
+//     Every survivor left unscored has true < T' <= T.  (qeps < 0 raises the bar above T'; it may
+//     pass phase A's lowest key, and phase B is then empty: phase A's rows are scored whatever
+//     their keys, which only costs.)
 //  Certificate: rows never listed (below the seed threshold thr0 or a workgroup's compaction bound
 //  drop) have true <= key_score(max(thr0, drop)) + qeps, which must be < T; and the rows scored
 //  must fit the block's RFW_CAP slots.
@@ -1563,7 +1602,9 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_wide(RefineArgs a, int KA
     const float* qv = a.q + (int64_t)q * a.d;
     if constexpr (QLDS)
         for (int i = tid; i < a.d; i += RF_THREADS) qs[(i & 7) * ng + (i >> 3)] = (double)qv[i];
-    // the key's margin: int8 keys carry theirs per query (upper bounds: true <= key + qeps); native
+    // the key's margin: int8 keys carry theirs per query (true <= key + qeps, qeps of either sign:
+    // everything below uses eps only through that inequality -- the phase-B bar T' - eps rounded
+    // down to a key, the certificate key(th) + eps < T -- and what L2 adds to it is >= 0); native
     // MFMA keys (qeps == null) are within the native screen's two-sided error of the true score
     // (the same bound as k_refine's certificate: fp32 accumulation + query rounding, times max ||x||)
     double eps = a.qeps ? (double)a.qeps[q]
@@ -1652,6 +1693,7 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_wide(RefineArgs a, int KA
         if (tid == 0) {
             a.pa_n[q] = nA;
             a.pa_tA[q] = tA;
+            if (a.rows) atomicAdd(a.rows, (unsigned long long)nA);
         }
         for (int j = tid; j < a.k; j += RF_THREADS) {
             const size_t o = (size_t)q * a.k + j, ost = a.ostride > 1 ? (size_t)a.ostride : 1;
@@ -1712,6 +1754,8 @@ __global__ void __launch_bounds__(RF_THREADS) k_refine_wide(RefineArgs a, int KA
     }
     const bool overflow = nA2 + nB > RFW_CAP;
     nB = min(nB, RFW_CAP - nA2);
+    // rows this block scores (vs_refine_rows_count): phase A where this launch ran it, phase B
+    if (tid == 0 && a.rows) atomicAdd(a.rows, (unsigned long long)((a.phase == 2 ? 0 : nA) + nB));
     __syncthreads();
     rfw_score<DT, METRIC, QLDS>(a, ids, sc, nA2, nA2 + nB, qs, qv);
     __syncthreads();
@@ -2154,18 +2198,19 @@ hipError_t launch_pack_qtile_i8(const float* q, int nqb, int d, int dpad8, uint8
                                 const unsigned* maxes, int* gcnt, u64* drop, hipStream_t st, int* fails,
                                 const unsigned* l2max, float gamma, const NativeTile* nat) {
     const NativeTile none{};
+    const int credit = i8_query_credit();
     if (!nat) {
         hipLaunchKernelGGL(k_pack_qtile_i8<0>, dim3(MFMA_QB), dim3(256), 0, st, q, nqb, d, dpad8, qt, qfac, qeps,
-                           maxes, gcnt, drop, fails, l2max, gamma, none);
+                           maxes, gcnt, drop, fails, l2max, gamma, none, credit);
         return hipGetLastError();
     }
     if (!nat->qt || !nat->qinfo || !nat->gcnt || !nat->drop || nat->dpad % 32 != 0) return hipErrorInvalidValue;
     if (nat->dt == DT_BF16)
         hipLaunchKernelGGL(k_pack_qtile_i8<DT_BF16>, dim3(MFMA_QB), dim3(256), 0, st, q, nqb, d, dpad8, qt, qfac,
-                           qeps, maxes, gcnt, drop, fails, l2max, gamma, *nat);
+                           qeps, maxes, gcnt, drop, fails, l2max, gamma, *nat, credit);
     else if (nat->dt == DT_F16)
         hipLaunchKernelGGL(k_pack_qtile_i8<DT_F16>, dim3(MFMA_QB), dim3(256), 0, st, q, nqb, d, dpad8, qt, qfac,
-                           qeps, maxes, gcnt, drop, fails, l2max, gamma, *nat);
+                           qeps, maxes, gcnt, drop, fails, l2max, gamma, *nat, credit);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();

@@ -138,6 +138,14 @@ int vs_set_k1_schedule(int32_t schedule) {
 }
 int vs_k1_schedule(void) { return k1_schedule(); }
 
+int vs_set_i8_query_credit(int32_t on) {
+    return guarded([&] {
+        if (on != 0 && on != 1) throw VsError(VS_ERR_ARG, "int8 query credit: 0 or 1");
+        set_i8_query_credit(on);
+    });
+}
+int vs_i8_query_credit(void) { return i8_query_credit(); }
+
 int vs_set_timing(vs_index* ix, int enable) {
     return guarded([&] {
         check_index(ix);
@@ -194,6 +202,19 @@ int64_t vs_full_scan_count(vs_index* ix) {
         unsigned u = 0;
         HIP_CHECK(hipMemcpy(&u, ix->d_unres, sizeof(unsigned), hipMemcpyDeviceToHost));
         v = u;
+    });
+    return rc == VS_OK ? v : rc;
+}
+
+int64_t vs_refine_rows_count(vs_index* ix) {
+    int64_t v = -1;
+    int rc = guarded([&] {
+        check_index(ix);
+        DeviceGuard dg(ix->device);
+        HIP_CHECK(hipDeviceSynchronize());
+        unsigned long long u = 0;
+        HIP_CHECK(hipMemcpy(&u, ix->d_maxsq + IX_REFINE_ROWS, sizeof(u), hipMemcpyDeviceToHost));
+        v = (int64_t)u;
     });
     return rc == VS_OK ? v : rc;
 }

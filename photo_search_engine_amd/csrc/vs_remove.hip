@@ -171,8 +171,7 @@ int vs_remove_ids(vs_index* ix, const uint8_t* bitmap, int64_t nbytes, int64_t* 
         if (n_new == 0) {  // every row: the state vs_reset leaves (capacity kept)
             HIP_CHECK(hipDeviceSynchronize());
             HIP_CHECK(hipMemsetAsync(ix->d_maxsq, 0, sizeof(unsigned), st));
-            HIP_CHECK(hipMemsetAsync(ix->d_maxsq + 2, 0, 2 * sizeof(unsigned), st));
-            HIP_CHECK(hipMemsetAsync(ix->d_maxsq + 5, 0, 3 * sizeof(unsigned), st));
+            reset_i8_stats(ix, st);
             HIP_CHECK(hipStreamSynchronize(st));
             ix->ntotal = 0;
             ix->reset_gen.fetch_add(1);

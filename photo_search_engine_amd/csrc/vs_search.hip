@@ -244,6 +244,7 @@ RefineArgs refine_base(const vs_index* ix, const float* q, const SearchOut& out,
     r.S64 = out.S64;
     r.cert = out.cert;
     r.ostride = out.ostride;
+    r.rows = (unsigned long long*)(ix->d_maxsq + IX_REFINE_ROWS);
     return r;
 }
 

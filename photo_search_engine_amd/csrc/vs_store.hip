@@ -148,6 +148,14 @@ void vs::quantize_rows(vs_index* ix, int64_t r0, int64_t n, hipStream_t st) {
                                 ix->d_maxsq + 2, st, ix->gmean));
 }
 
+// the int8 copy's statistics before every row is quantised anew: the maxima at 0, the minimum of
+// ||s c|| at +inf (stream-ordered on st)
+void vs::reset_i8_stats(vs_index* ix, hipStream_t st) {
+    HIP_CHECK(hipMemsetAsync(ix->d_maxsq + 2, 0, 2 * sizeof(unsigned), st));
+    HIP_CHECK(hipMemsetAsync(ix->d_maxsq + 5, 0, 3 * sizeof(unsigned), st));
+    HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)(ix->d_maxsq + 2 + I8_MIN_XH), (int)F32_INF_BITS, 1, st));
+}
+
 void vs::refresh_maxsq(vs_index* ix) {
     unsigned bits[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     HIP_CHECK(hipMemcpyAsync(bits, ix->d_maxsq, sizeof(bits), hipMemcpyDeviceToHost, ix->own));
@@ -279,11 +287,14 @@ int vs_create(int d, int metric, int dtype, int device, vs_index** out) {
             HIP_CHECK(hipStreamCreateWithFlags(&ix->own, hipStreamNonBlocking));
             // [0] max ||x||^2, [1] uncertified counter, [2..3] int8 screen maxima (fp32 bits),
             // [4] full-scan counter (vs_full_scan_count), [5..6] group residuals (max ||mu_g||,
-            // groups with a mean), [7] max ||x - s c|| of the int8 codes
-            HIP_CHECK(hipMalloc(&ix->d_maxsq, sizeof(unsigned) * 8));
-            HIP_CHECK(hipMemset(ix->d_maxsq, 0, sizeof(unsigned) * 8));
+            // groups with a mean), [7] max ||x - s c|| of the int8 codes, [8] min ||s c|| (+inf
+            // until a row is quantised), [10..11] rows scored by k_refine_wide (vs_internal.h IX_WORDS)
+            HIP_CHECK(hipMalloc(&ix->d_maxsq, sizeof(unsigned) * IX_WORDS));
+            HIP_CHECK(hipMemset(ix->d_maxsq, 0, sizeof(unsigned) * IX_WORDS));
             ix->d_uncert = ix->d_maxsq + 1;
             ix->d_unres = ix->d_maxsq + 4;
+            reset_i8_stats(ix, ix->own);
+            HIP_CHECK(hipStreamSynchronize(ix->own));
         } catch (...) {
             delete ix;
             throw;
@@ -320,8 +331,7 @@ int vs_reset(vs_index* ix) {
         ix->i8_bmax = 0.0f;
         ix->i8_res = false;
         HIP_CHECK(hipMemsetAsync(ix->d_maxsq, 0, sizeof(unsigned), ix->own));
-        HIP_CHECK(hipMemsetAsync(ix->d_maxsq + 2, 0, 2 * sizeof(unsigned), ix->own));
-        HIP_CHECK(hipMemsetAsync(ix->d_maxsq + 5, 0, 3 * sizeof(unsigned), ix->own));
+        reset_i8_stats(ix, ix->own);
         HIP_CHECK(hipStreamSynchronize(ix->own));
     });
 }
@@ -441,8 +451,7 @@ int vs_set_screen(vs_index* ix, int screen) {
         ix->screen = VS_SCREEN_I8;
         ix->dpad8 = (int)std::max<int64_t>(round_up(ix->d, 64), 128);  // >= 2 K-steps per tile (see dpad)
         try {
-            HIP_CHECK(hipMemsetAsync(ix->d_maxsq + 2, 0, 2 * sizeof(unsigned), ix->own));
-            HIP_CHECK(hipMemsetAsync(ix->d_maxsq + 5, 0, 3 * sizeof(unsigned), ix->own));
+            reset_i8_stats(ix, ix->own);
             ensure_capacity_i8(ix);
             quantize_rows(ix, 0, ix->ntotal, ix->own);
             HIP_CHECK(hipStreamSynchronize(ix->own));

@@ -955,6 +955,11 @@ class FlatIndex:
         """First-pass certificate failures so far (each one was re-searched)."""
         return int(check(self._L.vs_uncertified_count(self._h)))
 
+    def refine_rows_count(self) -> int:
+        """Stored rows the adaptive exact refine has scored so far, over all queries (include/vs.h
+        ``vs_refine_rows_count``)."""
+        return int(check(self._L.vs_refine_rows_count(self._h)))
+
     def screen_state(self) -> dict:
         """The screen's state (include/vs.h ``vs_screen_state``): group residuals, the int8 margins'
         maxima and the screen-health feedback (int8 union depth, native routing, native seed depth)."""
@@ -1089,6 +1094,17 @@ def set_k1_schedule(schedule: int) -> None:
 
 def k1_schedule() -> int:
     return int(_lib.load().vs_k1_schedule())
+
+
+def set_i8_query_credit(on: bool) -> None:
+    """The int8 screen's query credit, process-wide (include/vs.h ``vs_set_i8_query_credit``): on
+    (default) = a query whose own int8 rounding error is below the share the rows' bounds carry for it
+    refines fewer rows.  Results are identical."""
+    check(_lib.load().vs_set_i8_query_credit(int(bool(on))))
+
+
+def i8_query_credit() -> bool:
+    return bool(_lib.load().vs_i8_query_credit())
 
 
 REMOVE_STAGING_DEFAULT = 256 << 20
