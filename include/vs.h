@@ -643,6 +643,87 @@ int vs_adjust_last_stats(vs_index* index, int64_t* out, int cap);
  * the adjusted rows and of the full scan (with the walk that reports its rows) */
 int vs_adjust_last_times(vs_index* index, double* out, int cap);
 
+/* ==== fused search =============================================================================
+ * "One ranking from several embeddings of one request": the reference embeds each alternative wording
+ * of a request, searches each one and merges the lists in Python, keeping a photo's higher score
+ * (core/searcher.py _maybe_expand_query_results :1352-1458, _maybe_reflect_query_results :1219-1298,
+ * _deduplicate_results :242-261).  Milvus hybrid_search over several requests, Qdrant prefetch + fusion
+ * and Elasticsearch's multiple knn clauses are this call; faiss has none.  Two rankings: ANY ("matches
+ * any of these wordings", a row's best score over the sub-queries) and ALL ("dog and beach", its worst
+ * score).  ALL cannot be assembled from per-query top-k lists -- a row good on every concept can be
+ * outside each concept's list -- so only the index can rank it exactly.
+ *
+ * Members: every stored row, with a selector (may be NULL) the rows it allows, under the rules of
+ * vs_search_sel (a stale selector is VS_ERR_ARG; rows added after it was made are not selected).
+ * Scores: q is host fp32 nq x m x d, fused query a has the sub-queries q[a][0..m).  S_j is the canonical
+ * fp64 score of a row with sub-query j, as vs_search defines it; better / worse are the metric's
+ * direction (inner product: larger is better, L2: smaller).  VS_FUSE_ANY: F = the best of S_0..S_{m-1};
+ * VS_FUSE_ALL: F = the worst.  No arithmetic touches a score: F is bit-equal to one of the S_j.
+ * (Sub-query weights are deliberately no part of the call: a rounded multiply can tie rows that are
+ * distinct under S_j, which breaks the list argument below.)
+ * Ranking: the members by F in the metric's direction, ties to the lower id.
+ * Outputs (host): D (nq x k) = (float)F, I (nq x k) = the row ids, which (nq x k, may be NULL) = the
+ * lowest j with S_j == F, D_sub (nq x k x m, may be NULL) = (float)S_j for every j.  Padded as
+ * vs_search pads; a padded which is -1, padded D_sub entries take the worst value.
+ * m = 1 under either mode is bit-equal to vs_search / vs_search_sel with which = 0; ANY equals the host
+ * merge of the m lists of vs_search(q_j, k) (union, best score per id, first k by (score, id));
+ * permuting the sub-queries changes only which and the order inside D_sub; repeating one changes
+ * nothing (which keeps the lower index).
+ *
+ * m < 1 or m > VS_FUSE_MAX_Q, a mode other than the two, k < 1 or k > min(3276, VS_FUSE_WALK_MAX / m),
+ * null q / D / I and a stale selector are VS_ERR_ARG before anything is launched; nq = 0 returns at
+ * once; an empty member set gives all padding.  Shared lock, one leased context, the call synchronises
+ * (the shape of vs_search_adjusted).  Scratch is counted in vs_device_bytes_live and freed before the
+ * call returns.
+ *
+ * Limits.  The walk kernel ranks at most VS_FUSE_WALK_MAX entries (m lists of L) in LDS, so a list is at
+ * most min(3276, VS_FUSE_WALK_MAX / m) long: the bound on k and the default depth limit.  Beside n
+ * entries (n rounded up to a power of two, 12 bytes each) the walk holds one sub-query as fp64 in
+ * 144 KiB of LDS: d <= 8 * floor((147456 - 12 n) / 64), which is d <= 6144 at n = VS_FUSE_WALK_MAX and
+ * d <= 12288 at n <= 4096.  A call whose deepest walk would not fit is VS_ERR_ARG (lower the limit with
+ * vs_set_fuse_depth).
+ *
+ * Tiers (the same bits under each).
+ * LISTS: the exact top-L list of every sub-query among the members (one batched search of nq m queries,
+ * under the selector where one is given), then a device walk over their union, one workgroup per fused
+ * query: every distinct candidate is rescored canonically against all m sub-queries (the staged fp32
+ * scores are never used), F, which and the m scores are formed, and the candidates are ranked by
+ * (F, id).
+ *   ANY is complete at L = min(k, members), the only list it ever needs (the depth settings do not
+ *   apply): were a row of the answer with F = S_j outside list j, k members would be better than it
+ *   under (S_j, id), and each of those has F at least as good, an equal F only at a lower id.
+ *   ALL takes L = first, then 4 L up to min(limit, members).  A member outside every list is, for every
+ *   j, no better than list j's last entry S_{j,L}, so its F is no better than U, the worst over j of
+ *   S_{j,L} (the walk's own rescoring).  Complete iff the lists held every member, or there are at least
+ *   k candidates and the k-th best candidate F is strictly better than U.  Queries open at the limit go
+ *   to SCAN.
+ * SCAN: a streaming scan, exact for any input, ties by the thousand included.  Each workgroup scans its
+ * share of the members in ascending id, scores every row against all m sub-queries in one pass over the
+ * row, reduces to F and keeps a bounded running top-k under (F, id); the walk then reports which and
+ * D_sub of the k winners.
+ * AUTO: ANY uses LISTS; ALL uses LISTS, then SCAN for what stays open.  vs_set_fuse_mode forces SCAN, or
+ * LISTS with the same fall-through. */
+#define VS_FUSE_MAX_Q 8
+#define VS_FUSE_WALK_MAX 8192
+enum { VS_FUSE_ANY = 0, VS_FUSE_ALL = 1 };
+int vs_search_fused(vs_index* index, const vs_sel* sel, const float* q /* host nq x m x d */, int64_t nq,
+                    int32_t m, int32_t mode, int32_t k, float* D, int64_t* I, int32_t* which, float* D_sub);
+#define VS_FUSE_AUTO 0
+#define VS_FUSE_LISTS 1
+#define VS_FUSE_SCAN 2
+int vs_set_fuse_mode(vs_index* index, int tier);
+/* list lengths ALL's walk is fed (tests; the same bits under every setting): first = 0 -> max(4 k, 64),
+ * limit = 0 -> min(3276, VS_FUSE_WALK_MAX / m); 1 <= first <= limit <= 3276, and a call cuts both to its
+ * own default limit */
+int vs_set_fuse_depth(vs_index* index, int32_t first, int32_t limit);
+/* last call on the handle, up to cap (6): {fused queries, complete after the first list, complete after
+ * a deeper list, answered by the scan, longest list walked, tier taken (VS_FUSE_LISTS / VS_FUSE_SCAN)} */
+int vs_fuse_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/fuse_timing.py): the last call on the handle, up to cap (6): ms of
+ * HIP-event time {list search, walk} of the first list and of the deeper lists, of the scan and of the
+ * walk that reports the scan's rows */
+int vs_fuse_last_times(vs_index* index, double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

@@ -699,6 +699,41 @@ hipError_t launch_adjust_walk(const AdjustWalkArgs& a, int nq, hipStream_t st);
 hipError_t launch_adjust_scan(const FullScanArgs& a, const AdjustRows& rows, const uint32_t* ids, int64_t m, int qy,
                               hipStream_t st);
 
+// ---- fused search (vs_fuse.hip) ------------------------------------------------------
+// A fused query is m sub-queries; a row's fused score F is the best (ANY) or the worst (ALL) of its m
+// canonical fp64 scores, bit-equal to one of them.
+constexpr int FUSE_MAX_Q = 8;                // = VS_FUSE_MAX_Q
+constexpr int FUSE_WALK_MAX = 8192;          // = VS_FUSE_WALK_MAX: entries of one walk (m lists of L)
+constexpr size_t FUSE_DYN_CAP = 144 * 1024;  // the walk's dynamic LDS: the entries' keys and ids, one sub-query as fp64
+enum { FUSE_ANY = 0, FUSE_ALL = 1 };
+struct FuseWalkArgs {
+    const uint8_t* corpus;  // tiled shard
+    int d, dpad, dt, metric;
+    int64_t n_valid;        // rows of the shard: an entry at or past it ends its list like an absent one
+    const float* q;         // [nq][m][d] fp32 sub-queries of the launch's fused queries
+    int m, mode;            // sub-queries per fused query (1..FUSE_MAX_Q); FUSE_ANY / FUSE_ALL
+    const int64_t* I_list;  // [nq][nl][L] lists of row ids, best first (an entry < 0 ends a list)
+    int nl;                 // lists per fused query: m (list j is sub-query j's exact ranking) or 1 (a scan's list)
+    int64_t L;              // nl * L <= FUSE_WALK_MAX
+    int certify;            // 1: complete as the ALL certificate says (nl == m); 0: always complete
+    int k;                  // (an answer shorter than k is padded)
+    double* S_tmp;          // [nq][nl L][m] scratch: the distinct entries' canonical scores
+    uint32_t* E_tmp;        // [nq][nl L] scratch: the distinct entries' ids, ascending
+    int64_t* I;             // [nq][k] rows by (F, id), -1 padded
+    float* D;               // [nq][k] (float)F, padded with the worst score
+    int32_t* which;         // [nq][k] the lowest j with S_j == F, -1 padded
+    float* D_sub;           // [nq][k][m] (float)S_j, padded with the worst score
+    int32_t* complete;      // [nq]
+};
+size_t fuse_walk_lds(int64_t n_entries, int d);  // dynamic LDS of one walk workgroup
+hipError_t launch_fuse_walk(const FuseWalkArgs& a, int nq, hipStream_t st);
+// the streaming scan ranking by F: a.q is [a.nq][m][d], every row scored against the m sub-queries in one
+// pass; ids null = rows [0, a.n_valid), else the n_ids listed rows (ascending, each < a.n_valid); a.G
+// workgroups split the sequence, qy (1..a.nq) slices deal the fused queries; a.I / a.cert as in
+// launch_sel_scan with a.all_queries set (a.D / a.S64 report F where given)
+hipError_t launch_fuse_scan(const FullScanArgs& a, int m, int mode, const uint32_t* ids, int64_t n_ids, int qy,
+                            hipStream_t st);
+
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
 // The index's device words (vs_index::d_maxsq): [0] max ||x||^2, [1] uncertified counter, [2..3] int8

@@ -1,14 +1,18 @@
 // vs_scan.h -- the streaming exact scan shared by k_full_scan (vs_fullscan.hip: every row of the
-// shard), k_sel_scan (vs_selscan.hip: the rows of a selector's ascending id list) and k_adjust_scan
-// (vs_adjust.hip: either sequence, ranked by a per-row affine function of the score): the bounded
-// running top-k under the total order (score, then id), its batch sort / rank merge, and the last
-// workgroup's merge of the per-workgroup lists (st_agent / ld_agent hand-off).
+// shard), k_sel_scan (vs_selscan.hip: the rows of a selector's ascending id list), k_adjust_scan
+// (vs_adjust.hip: either sequence, ranked by a per-row affine function of the score) and k_fuse_scan
+// (vs_fuse.hip: either sequence, each row scored against several sub-queries at once and ranked by the
+// best or the worst of those scores): the bounded running top-k under the total order (score, then id),
+// its batch sort / rank merge, and the last workgroup's merge of the per-workgroup lists (st_agent /
+// ld_agent hand-off).
 //
 // Workgroup b scans positions [n b / G, n (b + 1) / G) of its row sequence -- row ids themselves
 // (SEL = false) or entries of the id list (SEL = true).  Either sequence ascends in id, so once a
 // workgroup's list is full a row tied with its k-th best never enters it: the memory stays O(k)
 // however many rows tie, and the merged answer is the k lowest ids among equal scores.
 #pragma once
+#include <type_traits>
+
 #include "vs_device.h"
 
 namespace vs {
@@ -110,9 +114,18 @@ inline size_t fs_lds_bytes(int k, int d, int* KL_out, bool* qlds_out) {
 // XF: what a row's canonical score becomes before the running top-k.  FsPlain ranks by the score itself
 // and compiles to nothing; an active transform (vs_adjust.hip) may pass a row over, or put another key
 // in the score's place -- the key is what the lists hold and what D / S64 report.
+// A fused transform (`static constexpr bool fused = true`, vs_fuse.hip) scores a row itself, against
+// xf.m sub-queries in one pass: a.q holds m vectors per query, load_queries stages them as fp64 (QLDS: m
+// times the query's LDS), and score_rows returns per row the one score the lists rank by.  It scores the
+// refine's rows per wave, not the scan's (m accumulators per row).  Every hook below is an `if constexpr`:
+// a transform that is not fused compiles to the code it had without them.
 struct FsPlain {
     static constexpr bool active = false;
 };
+template <class XF, class = void>
+struct fs_fused : std::false_type {};
+template <class XF>
+struct fs_fused<XF, std::void_t<decltype(XF::fused)>> : std::bool_constant<XF::fused> {};
 template <int DT, int METRIC, bool QLDS, bool SEL, class XF = FsPlain>
 __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, const uint32_t* __restrict__ sel_ids,
                                              int64_t sel_m, const XF& xf = XF()) {
@@ -126,16 +139,19 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
     L.lsc[1] = L.lsc[0] + KL;
     L.bsc = L.lsc[1] + KL;
     double* qs = L.bsc + FS_B;
-    L.lid[0] = (uint32_t*)(qs + (QLDS ? (size_t)ng * 8 : 0));
+    constexpr bool FUSED = fs_fused<XF>::value;
+    if constexpr (FUSED) L.lid[0] = (uint32_t*)(qs + (QLDS ? (size_t)ng * 8 * xf.m : 0));
+    else L.lid[0] = (uint32_t*)(qs + (QLDS ? (size_t)ng * 8 : 0));
     L.lid[1] = L.lid[0] + KL;
     L.bid = L.lid[1] + KL;
     __shared__ int go_s, nb_s, last_s;
     __shared__ int red_s[FS_NW];
-    constexpr int RR = fs_rows<DT>();
+    constexpr int RR = FUSED ? refine_rows<DT>() : fs_rows<DT>();
     const int k = a.k;
     const int64_t nseq = SEL ? sel_m : a.n_valid;
     const int64_t r0 = nseq * b / G, r1 = nseq * (b + 1) / G;
-    const int qfirst = SEL ? (int)blockIdx.y : 0, qstep = SEL ? (int)gridDim.y : 1;
+    constexpr bool QY = SEL || FUSED;  // (a fused scan deals its queries over the grid's y dimension either way)
+    const int qfirst = QY ? (int)blockIdx.y : 0, qstep = QY ? (int)gridDim.y : 1;
     for (int q = qfirst; q < a.nq; q += qstep) {
         __syncthreads();  // (the previous query's readers of qs / the lists are done)
         if (tid == 0) {
@@ -145,8 +161,12 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
         __syncthreads();
         if (!go_s) continue;
         const float* qv = a.q + (int64_t)q * a.d;
-        if constexpr (QLDS)
-            for (int i = tid; i < a.d; i += FS_THREADS) qs[(i & 7) * ng + (i >> 3)] = (double)qv[i];
+        if constexpr (FUSED) qv = a.q + (int64_t)q * a.d * xf.m;
+        if constexpr (QLDS) {
+            if constexpr (FUSED) xf.load_queries(qs, qv, a.d, ng, tid);
+            else
+                for (int i = tid; i < a.d; i += FS_THREADS) qs[(i & 7) * ng + (i >> 3)] = (double)qv[i];
+        }
         __syncthreads();
         int cur = 0, nl = 0;
         for (int64_t base = r0; base < r1; base += FS_NW * RR) {
@@ -159,7 +179,8 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
             }
             if (rr[0] >= 0) {  // (wave-uniform)
                 double s4[RR];
-                exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s4);
+                if constexpr (FUSED) xf.template score_rows<DT, METRIC, QLDS, RR>(a, rr, qs, qv, lane, s4);
+                else exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s4);
                 if (lane == 0) {
                     const bool full = nl >= k;
                     const double ts = full ? L.lsc[cur][k - 1] : 0.0;

@@ -1,6 +1,7 @@
 // vs_walk.h -- what the jobs built as "an exact ranking, then a device walk over it" share on the host
-// (vs_diverse_host.hip, vs_group_host.hip): the driver of tiers 1 and 2, which deepens
-// the lists until the walk is complete, the HIP-event stopwatch and the carving of a walk's output block.
+// (vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip, vs_fuse_host.hip): the
+// driver of tiers 1 and 2, which deepens the lists until the walk is complete, the HIP-event stopwatch and
+// the carving of a walk's output block.
 #pragma once
 #include "vs_index.h"
 
@@ -83,9 +84,14 @@ struct Deepened {
 // staged chunk of m queries, walk(so, L, m, idx, &ev) walks the device lists so.Id / so.Dd [m][L], puts
 // query j's answer where the caller's query idx[j] belongs and records ev behind its last kernel;
 // done(query) says whether that answer is complete (a list that held every member always is).
+// unit > 1 (the fused search): a caller's query is `unit` consecutive rows of q, searched as unit plain
+// queries that always travel in one staged chunk -- so.Id / so.Dd are [m unit][L], and m, idx and done
+// count the caller's queries.
 template <typename Walk, typename Done>
 Deepened deepen_lists(vs_index* ix, Ctx* c, hipStream_t st, const vs_sel* sel, int64_t members, int64_t first,
-                      int64_t limit, const float* q, int64_t nq, WalkTimes& times, Walk&& walk, Done&& done) {
+                      int64_t limit, const float* q, int64_t nq, WalkTimes& times, Walk&& walk, Done&& done,
+                      int64_t unit = 1) {
+    const int64_t qd = unit * ix->d;  // floats of one caller's query
     const int64_t Lmax = std::min<int64_t>(limit, members);
     int64_t L = std::min<int64_t>(first, Lmax);
     DevEvent e0(hipEventDefault), e1(hipEventDefault), e2(hipEventDefault);
@@ -99,21 +105,22 @@ Deepened deepen_lists(vs_index* ix, Ctx* c, hipStream_t st, const vs_sel* sel, i
         const int64_t n = (int64_t)pending.size();
         const float* qp = q;
         if (tier) {  // the queries not done as one batch
-            qsub.resize((size_t)n * ix->d);
+            qsub.resize((size_t)n * qd);
             for (int64_t j = 0; j < n; ++j)
-                std::copy(q + pending[(size_t)j] * ix->d, q + (pending[(size_t)j] + 1) * ix->d, qsub.begin() + j * ix->d);
+                std::copy(q + pending[(size_t)j] * qd, q + (pending[(size_t)j] + 1) * qd, qsub.begin() + j * qd);
             qp = qsub.data();
         }
         const int kk = (int)L;
-        const SelPlan plan = sel ? sel_plan(ix, sel, n, kk) : SelPlan{0, 0};
-        const int64_t chunk = stage_chunk(ix, n, kk, !sel);
+        const SelPlan plan = sel ? sel_plan(ix, sel, n * unit, kk) : SelPlan{0, 0};
+        const int64_t chunk = unit == 1 ? stage_chunk(ix, n, kk, !sel)
+                                        : std::max<int64_t>(1, stage_chunk(ix, n * unit, kk, !sel) / unit);
         next.clear();
         for (int64_t q0 = 0; q0 < n; q0 += chunk) {
             const int64_t m = std::min(chunk, n - q0);
             const int64_t* idx = pending.data() + q0;
             HIP_CHECK(hipEventRecord(e0, st));
-            stage_queries(ix, c, qp, q0, m, st);
-            const StagedOut so = exact_lists(ix, c, sel, plan, m, kk, LISTS_DEVICE, st);
+            stage_queries(ix, c, qp, q0 * unit, m * unit, st);
+            const StagedOut so = exact_lists(ix, c, sel, plan, m * unit, kk, LISTS_DEVICE, st);
             HIP_CHECK(hipEventRecord(e1, st));
             walk(so, L, m, idx, &e2);
             times.search(tier) += ms_between(e0, e1);

@@ -376,6 +376,9 @@ class Groups:
 
 
 ADJUST_MODES = {"auto": 0, "direct": 1, "bound": 2, "scan": 3}  # VS_ADJUST_*
+FUSE_KINDS = {"any": 0, "all": 1}  # VS_FUSE_ANY / VS_FUSE_ALL
+FUSE_MODES = {"auto": 0, "lists": 1, "scan": 2}  # VS_FUSE_*
+FUSE_MAX_Q = 8  # VS_FUSE_MAX_Q
 
 
 def adjust_arrays(n: int, scale=None, bias=None):
@@ -785,6 +788,63 @@ class FlatIndex:
         check(self._L.vs_adjust_last_times(self._h, buf, 6))
         return {"search_ms": [float(buf[0]), float(buf[2])], "walk_ms": [float(buf[1]), float(buf[3])],
                 "direct_scan_ms": float(buf[4]), "full_scan_ms": float(buf[5])}
+
+    def search_fused(self, q, k: int, mode: str = "any", sel=None, return_sub: bool = False):
+        """Exact top-``k`` of fused queries (``vs_search_fused``, include/vs.h): ``q`` is ``(nq, m, d)``, one
+        fused query per ``m`` sub-queries (``1 <= m <= 8``).  Every member -- every row, under ``sel`` the
+        rows it allows -- is ranked by ``F``, its best (``mode="any"``) or its worst (``mode="all"``) score
+        over the sub-queries, in the metric's direction, ties to the lower id.  Returns ``(D, I, which)``,
+        ``D`` the fused scores and ``which`` the lowest sub-query index whose score is ``F``, and with
+        ``return_sub`` ``(D, I, which, D_sub)``, ``D_sub`` ``(nq, k, m)`` the row's score under every
+        sub-query.  ``k`` is at most ``min(3276, 8192 // m)``."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 3 or q.shape[2] != self.d:
+            raise ValueError(f"search_fused expects an (nq, m, {self.d}) array, got {q.shape}")
+        if mode not in FUSE_KINDS:
+            raise ValueError(f"fuse mode must be one of {sorted(FUSE_KINDS)}")
+        nq, m, k = q.shape[0], q.shape[1], int(k)
+        if not 1 <= m <= FUSE_MAX_Q:
+            raise ValueError(f"search_fused takes 1..{FUSE_MAX_Q} sub-queries per fused query, got {m}")
+        if k < 1:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "k must be >= 1")
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        W = np.empty((nq, k), dtype=np.int32)
+        U = np.empty((nq, k, m), dtype=np.float32) if return_sub else None
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_search_fused(self._h, sh, _ptr(q), nq, m, FUSE_KINDS[mode], k, _ptr(D), _ptr(I), _ptr(W),
+                                          _ptr(U) if return_sub else None))
+        return (D, I, W, U) if return_sub else (D, I, W)
+
+    def set_fuse_mode(self, mode: str) -> None:
+        """Force the tier of fused searches (``"lists"``, ``"scan"``) or let the library choose
+        (``"auto"``); the same bits under every mode (``vs_set_fuse_mode``)."""
+        if mode not in FUSE_MODES:
+            raise ValueError(f"fuse tier must be one of {sorted(FUSE_MODES)}")
+        check(self._L.vs_set_fuse_mode(self._h, FUSE_MODES[mode]))
+
+    def set_fuse_depth(self, first: int = 0, limit: int = 0) -> None:
+        """The list lengths ``mode="all"`` of :meth:`search_fused` walks: the first list and the longest one
+        (``0`` = the defaults; the same bits under every setting, ``vs_set_fuse_depth``)."""
+        check(self._L.vs_set_fuse_depth(self._h, int(first), int(limit)))
+
+    def fuse_last_stats(self) -> dict:
+        """The last :meth:`search_fused`: fused queries, how many were complete after the first list, after a
+        deeper list, how many the scan answered, the longest list walked and the tier taken
+        (``vs_fuse_last_stats``)."""
+        buf = (ctypes.c_int64 * 6)()
+        check(self._L.vs_fuse_last_stats(self._h, buf, 6))
+        tier = {v: n for n, v in FUSE_MODES.items()}[int(buf[5])]
+        return {"queries": int(buf[0]), "first": int(buf[1]), "deeper": int(buf[2]), "scan": int(buf[3]),
+                "longest": int(buf[4]), "tier": tier}
+
+    def fuse_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`search_fused`: list search and walk per list tier, the
+        scan and the walk that reports its rows (``vs_fuse_last_times``)."""
+        buf = (ctypes.c_double * 6)()
+        check(self._L.vs_fuse_last_times(self._h, buf, 6))
+        return {"search_ms": [float(buf[0]), float(buf[2])], "walk_ms": [float(buf[1]), float(buf[3])],
+                "scan_ms": float(buf[4]), "scan_walk_ms": float(buf[5])}
 
     def set_range_mode(self, mode: str) -> None:
         """Force the tier of range searches (``"scan"``, ``"screen"`` where it applies) or let the

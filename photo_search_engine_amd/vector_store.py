@@ -471,6 +471,49 @@ class VectorStore:
                  "vector_score": (float(d) + 1.0) / 2.0, "keyword_score": hits.get(index)}
                 for a, index, d in zip(A[0].tolist(), I[0].tolist(), D[0].tolist()) if index != -1]
 
+    def search_any(self, query_embeddings: List[List[float]], top_k: int, allowed=None) -> List[Dict]:
+        """:meth:`search` with several embeddings of one request -- its alternative wordings (an addition at
+        the boundary; Milvus ``hybrid_search``, Qdrant prefetch + fusion, Elasticsearch's multiple ``knn``
+        clauses): every item ranked by its best score over the embeddings, exactly, in one call.  It is
+        what the reference assembles from one :meth:`search` per wording and a merge in Python that keeps
+        a photo's higher score (core/searcher.py ``_maybe_expand_query_results`` :1352-1458,
+        ``_maybe_reflect_query_results`` :1219-1298, ``_deduplicate_results`` :242-261).  Each result is
+        :meth:`search`'s dict (``distance`` = the best score) plus ``"matched_query"``, the index of the
+        first embedding that gives that score, and ``"distances"``, the item's score under every
+        embedding.  Each embedding is normalised as :meth:`search` normalises its one; the guards and the
+        ``k = min(top_k, ntotal)`` clamp are :meth:`search`'s; ``allowed`` as there.  An empty list of
+        embeddings raises ``ValueError``; at most 8 embeddings, and ``top_k`` at most
+        ``min(3276, 8192 // len(query_embeddings))``."""
+        return self._search_fused(query_embeddings, top_k, "any", allowed)
+
+    def search_all(self, query_embeddings: List[List[float]], top_k: int, allowed=None) -> List[Dict]:
+        """:meth:`search_any` for a compound request ("dog *and* beach"): every item ranked by its worst
+        score over the embeddings, so an item is as good as its weakest concept.  No merge of per-concept
+        lists gives this ranking -- an item good on every concept can be outside each concept's list --
+        but the index ranks every item.  Results as :meth:`search_any` (``distance`` = the worst score,
+        ``matched_query`` = the concept that gives it)."""
+        return self._search_fused(query_embeddings, top_k, "all", allowed)
+
+    def _search_fused(self, query_embeddings, top_k: int, mode: str, allowed) -> List[Dict]:
+        embeddings = list(query_embeddings)
+        if not embeddings:
+            raise ValueError("query_embeddings must hold at least one embedding")
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        for embedding in embeddings:
+            if len(embedding) != self.dimension:
+                raise ValueError(f"向量维度不匹配: {len(embedding)} != {self.dimension}")
+        if not hasattr(self.index, "search_fused"):
+            raise NotImplementedError("search_any / search_all need a one-device flat index")
+        k = min(int(top_k), int(self.index.ntotal))
+        q = np.stack([self._normalize_query(embedding)[0] for embedding in embeddings])[None, :, :]
+        sel = None if allowed is None else self._allowed_rows(allowed)
+        D, I, W, U = self.index.search_fused(q, k, mode=mode, sel=sel, return_sub=True)
+        return [{"metadata": self.metadata[index], "distance": float(distance), "matched_query": int(which),
+                 "distances": [float(s) for s in sub]}
+                for distance, index, which, sub in zip(D[0].tolist(), I[0].tolist(), W[0].tolist(), U[0].tolist())
+                if index != -1]
+
     def _group_keys(self, group_by, n: int):
         """``(groups, values, own)`` of a ``group_by``: the index's group keys object, the value each
         non-negative key stands for (``None``: the key itself), and whether the caller closes the object (a cached one stays)."""
