@@ -724,6 +724,73 @@ int vs_fuse_last_stats(vs_index* index, int64_t* out, int cap);
  * walk that reports the scan's rows */
 int vs_fuse_last_times(vs_index* index, double* out, int cap);
 
+/* ==== paged search =============================================================================
+ * "Load more": continue a ranking after a cursor row.  Every ranking above stops at k <= 3276; this call
+ * returns the k rows that follow a given row of vs_search's ranking, exactly, at any depth, without
+ * state on either side (Elasticsearch from/size and search_after, Qdrant offset, Milvus offset and its
+ * search iterator, Weaviate after; faiss has none).
+ *
+ * Members: every stored row, with a selector (may be NULL) the rows it allows, under the rules of
+ * vs_search_sel (a stale selector is VS_ERR_ARG; rows added after it was made are not selected).
+ * Cursor: after[q] = c >= 0 names a stored row; with S* the canonical fp64 score of row c (the values
+ * vs_reconstruct returns) with query q, the cursor is the position (S*, c) in vs_search's total order
+ * (score in the metric's direction, then the lower id).  Row c need not be a member -- the selector may
+ * disallow it, or it may have been added after the selector was made: the position is defined either way.
+ * after[q] = -1 is the position before every row.
+ * Answer: the members that rank strictly after the cursor -- a worse S, or an equal S and an id > c -- the
+ * first k of them in the total order; D = (float)S, exactly what vs_search reports for the row; padded as
+ * vs_search pads (-1, -FLT_MAX / +FLT_MAX).  "Equal" and "worse" are numeric comparisons of doubles, the
+ * ones the scans' running top-k uses: +0.0 and -0.0 tie and the id decides.
+ * rank[q] (may be NULL): the members at or before the cursor, i.e. the 0-based position, in the members'
+ * ranking, of the first returned row; 0 for after = -1, the member count when nothing is left.
+ * Identities: after = -1 is bit-equal to vs_search / vs_search_sel; pages chained by "after = the last id
+ * of the previous page" concatenate to the members' whole ranking (vs_range_search with an infinite
+ * radius), rank of each page being the rows returned so far; a page with fewer than k rows ends it.
+ * rank_hint[q] (array may be NULL; -1 = unknown): the caller's guess of rank[q] -- an iterator knows it,
+ * the previous rank plus the rows returned.  It changes the work only, never the bits: a wrong hint costs
+ * deeper lists or a scan, never a wrong row.
+ *
+ * k < 1 or k > 3276, null q / after / D / I, after[q] < -1 or >= ntotal (on an empty index only -1 is
+ * legal), a stale selector and d > 14336 (the cut kernel stages the query as fp64 in LDS) are VS_ERR_ARG
+ * before anything is launched; nq = 0 returns at once; an empty member set gives all padding and rank 0.
+ * Shared lock, one leased context, the call synchronises (the shape of vs_search_adjusted).  Scratch is
+ * counted in vs_device_bytes_live and freed before the call returns.
+ * Not covered: the caller must pass the same query bits on every page of a chain (S* is recomputed from
+ * them); ids shift after vs_remove_ids, so a cursor taken before a removal names another row.
+ *
+ * Tiers (the same bits under each).  The cursor rows are scored first, one wave per query.
+ * LISTS: the exact top-L list of every query among the members, then a cut kernel, one workgroup per
+ * query, that finds p, the list's entries at or before the cursor.  Rounding to fp32 is monotone, so an
+ * entry whose staged D is strictly better (worse) than (float)S* is before (after) the cursor; only the
+ * entries with D == (float)S* are rescored canonically and compared by (S, id).  The page is entries
+ * p .. p+k-1 as staged and rank = p; complete iff L - p >= k or the list held every member, else the
+ * list is re-searched at 4 L up to min(limit, members).  The first list is max(first, rank_hint + k) over
+ * the batch's hinted queries when that is within the limit.
+ * SCAN: the streaming scan of the members in ascending id with the rows at or before the cursor passed
+ * over and counted into rank; exact for any input -- cursors beyond the limit, rows tied with the cursor
+ * by the thousand.
+ * AUTO: a query whose rank_hint + k exceeds the limit goes straight to SCAN, the others to LISTS; what is
+ * open at the limit goes to SCAN.  vs_set_after_mode forces SCAN, or LISTS with the same fall-through
+ * (hints beyond the limit are then ignored). */
+int vs_search_after(vs_index* index, const vs_sel* sel, const float* q, int64_t nq, int32_t k,
+                    const int64_t* after /* host nq */, const int64_t* rank_hint /* host nq, may be NULL */,
+                    float* D, int64_t* I /* host nq x k */, int64_t* rank /* host nq, may be NULL */);
+#define VS_AFTER_AUTO 0
+#define VS_AFTER_LISTS 1
+#define VS_AFTER_SCAN 2
+int vs_set_after_mode(vs_index* index, int tier);
+/* list lengths the cut is fed (tests; the same bits under every setting): first = 0 -> max(4 k, 64),
+ * limit = 0 -> 3276 (vs_search's k limit); 1 <= first <= limit <= 3276 */
+int vs_set_after_depth(vs_index* index, int32_t first, int32_t limit);
+/* last call on the handle, up to cap (6): {queries, complete after the first list, complete after a
+ * deeper list, answered by the scan, longest list walked, tier taken (VS_AFTER_SCAN when forced, else
+ * VS_AFTER_LISTS: under AUTO the scan's share is the fourth number)} */
+int vs_after_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/after_timing.py): the last call on the handle, up to cap (6): ms of HIP-event
+ * time {list search, cut} of the first list and of the deeper lists, of the cursor scoring and of the
+ * scan */
+int vs_after_last_times(vs_index* index, double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

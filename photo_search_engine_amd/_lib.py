@@ -159,6 +159,12 @@ _SIGS = {
     "vs_set_fuse_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
     "vs_fuse_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_fuse_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    # paged search
+    "vs_search_after": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "vs_set_after_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "vs_set_after_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
+    "vs_after_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_after_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

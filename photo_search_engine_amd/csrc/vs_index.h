@@ -1,7 +1,7 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
 // vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip,
-// vs_fuse_host.hip; the last four share the list-deepening driver of vs_walk.h).
+// vs_fuse_host.hip, vs_after_host.hip; the last five share the list-deepening driver of vs_walk.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -70,7 +70,7 @@ struct Ctx {
     }
 };
 
-// A walk job on the index (diversified, grouped, adjusted, fused search): the list lengths set by the caller
+// A walk job on the index (diversified, grouped, adjusted, fused, paged search): the list lengths set by the caller
 // (0 = the defaults) and what the last call reported, stats[] and its HIP-event ms times[].
 struct WalkState {
     std::atomic<int> first{0}, limit{0};
@@ -180,6 +180,11 @@ struct vs_index {
     // (vs_fuse_last_stats) and its ms {search, walk} per list tier, scan, the scan's walk (vs_fuse_last_times)
     vs::WalkState fu;
     std::atomic<int> fuse_mode{VS_FUSE_AUTO};
+    // paged search (vs_set_after_depth, vs_set_after_mode): the last call's {queries, complete after the
+    // first list, after a deeper list, answered by the scan, longest list walked, tier taken}
+    // (vs_after_last_stats) and its ms {search, cut} per list tier, cursor scoring, scan (vs_after_last_times)
+    vs::WalkState af;
+    std::atomic<int> after_mode{VS_AFTER_AUTO};
     int last_kernel_kind = 0;  // 1 = mfma, 2 = gemv, 3 = int8 mfma, 4 = int8 gemv, 5 = exact full scan
     // Screen health (first passes of MFMA batches): the certificate-failure count of a batch is read
     // back without a host wait (pinned word + event, observed by a later search).  A failed query

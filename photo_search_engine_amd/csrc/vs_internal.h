@@ -734,6 +734,43 @@ hipError_t launch_fuse_walk(const FuseWalkArgs& a, int nq, hipStream_t st);
 hipError_t launch_fuse_scan(const FullScanArgs& a, int m, int mode, const uint32_t* ids, int64_t n_ids, int qy,
                             hipStream_t st);
 
+// ---- paged search (vs_after.hip) -----------------------------------------------------
+// A query's cursor is the position (S*, c) in vs_search's total order: c a stored row (or -1: from the
+// top), S* its canonical fp64 score with the query.  On the device S* is held as the scan's key, S or -S
+// for L2, so "better" is always "greater" (fs_better).
+constexpr int AF_THREADS = 256;  // k_after_cut: one workgroup per query
+constexpr int AF_D_MAX = 14336;  // the cut kernel stages the query as fp64 in LDS (112 KiB at this d)
+struct AfterCursor {
+    const int64_t* id;    // [the call's queries] cursor row, -1 = from the top
+    const double* key;    // [the call's queries] its key (unused where id is -1)
+    const int64_t* qmap;  // [nq of the launch] the call's query behind launch query j (null: the identity)
+};
+// key[j] = the key of row after[j] with query j (after[j] < 0: 0); one wave per query
+hipError_t launch_after_score(int dt, int metric, const uint8_t* corpus, int d, int dpad, int64_t n_valid, const float* q,
+                              const int64_t* after, int64_t nq, double* key, hipStream_t st);
+struct AfterCutArgs {
+    const uint8_t* corpus;  // tiled shard
+    int d, dpad, dt, metric;
+    int64_t n_valid;        // rows of the shard: an entry at or past it ends the list like an absent one
+    const float* q;         // [nq][d] fp32 queries of the launch
+    const int64_t* I_list;  // [nq][L] each query's exact ranking among the members, best first (an entry < 0 ends it)
+    const float* D_list;    // [nq][L] the scores vs_search reports for them: (float)S
+    int64_t L;
+    AfterCursor cur;
+    int k;
+    int64_t* I;             // [nq][k] the list's entries p .. p + k - 1, -1 padded
+    float* D;               // [nq][k] their D_list, padded with the worst score
+    int64_t* rank;          // [nq] p: the list's entries at or before the cursor
+    int32_t* complete;      // [nq] 1: k entries behind the cursor, or the list ended before L (it held every member)
+};
+hipError_t launch_after_cut(const AfterCutArgs& a, int nq, hipStream_t st);
+// fs_scan_body over the rows strictly after each query's cursor: ids null = rows [0, a.n_valid), else the m
+// listed rows (ascending, each < a.n_valid); every row of the sequence at or before the cursor is passed
+// over and counted into rank[q] (zeroed by the caller); a.G, qy, a.cert / a.all_queries as in
+// launch_sel_scan; cur is indexed by the launch's queries through cur.qmap
+hipError_t launch_after_scan(const FullScanArgs& a, const AfterCursor& cur, unsigned long long* rank, const uint32_t* ids,
+                             int64_t m, int qy, hipStream_t st);
+
 constexpr int I8_GROUP_ROWS = 4096;  // rows per group of the int8 copy's group residuals (16 tiles)
 constexpr int I8_MAX_K = 1024;  // largest k the int8 screen serves (k_refine_wide: 2 * KA <= RFW_CAP)
 // The index's device words (vs_index::d_maxsq): [0] max ||x||^2, [1] uncertified counter, [2..3] int8

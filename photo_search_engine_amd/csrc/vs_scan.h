@@ -1,8 +1,9 @@
 // vs_scan.h -- the streaming exact scan shared by k_full_scan (vs_fullscan.hip: every row of the
 // shard), k_sel_scan (vs_selscan.hip: the rows of a selector's ascending id list), k_adjust_scan
-// (vs_adjust.hip: either sequence, ranked by a per-row affine function of the score) and k_fuse_scan
+// (vs_adjust.hip: either sequence, ranked by a per-row affine function of the score), k_fuse_scan
 // (vs_fuse.hip: either sequence, each row scored against several sub-queries at once and ranked by the
-// best or the worst of those scores): the bounded running top-k under the total order (score, then id),
+// best or the worst of those scores) and k_after_scan (vs_after.hip: either sequence, the rows at or
+// before a query's cursor passed over and counted): the bounded running top-k under the total order (score, then id),
 // its batch sort / rank merge, and the last workgroup's merge of the per-workgroup lists (st_agent /
 // ld_agent hand-off).
 //
@@ -117,11 +118,19 @@ inline size_t fs_lds_bytes(int k, int d, int* KL_out, bool* qlds_out) {
 // A fused transform (`static constexpr bool fused = true`, vs_fuse.hip) scores a row itself, against
 // xf.m sub-queries in one pass: a.q holds m vectors per query, load_queries stages them as fp64 (QLDS: m
 // times the query's LDS), and score_rows returns per row the one score the lists rank by.  It scores the
-// refine's rows per wave, not the scan's (m accumulators per row).  Every hook below is an `if constexpr`:
-// a transform that is not fused compiles to the code it had without them.
+// refine's rows per wave, not the scan's (m accumulators per row).
+// A per-query transform (`static constexpr bool per_query = true`, vs_after.hip) gets the query's index
+// in its key hook and may count the rows it passes over: key(q, id, s, passed) adds to the lane's
+// `passed`, and count(q, n) takes the workgroup's sum once per query.
+// Every hook below is an `if constexpr`: a transform that is neither compiles to the code it had without
+// them.
 struct FsPlain {
     static constexpr bool active = false;
 };
+template <class XF, class = void>
+struct fs_per_query : std::false_type {};
+template <class XF>
+struct fs_per_query<XF, std::void_t<decltype(XF::per_query)>> : std::bool_constant<XF::per_query> {};
 template <class XF, class = void>
 struct fs_fused : std::false_type {};
 template <class XF>
@@ -146,6 +155,8 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
     L.bid = L.lid[1] + KL;
     __shared__ int go_s, nb_s, last_s;
     __shared__ int red_s[FS_NW];
+    constexpr bool PERQ = fs_per_query<XF>::value;
+    __shared__ unsigned passed_s;  // (PERQ: the rows this workgroup's transform passed over and counted)
     constexpr int RR = FUSED ? refine_rows<DT>() : fs_rows<DT>();
     const int k = a.k;
     const int64_t nseq = SEL ? sel_m : a.n_valid;
@@ -157,6 +168,7 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
         if (tid == 0) {
             go_s = (a.all_queries || a.cert[q] == 0) ? 1 : 0;
             nb_s = 0;
+            if constexpr (PERQ) passed_s = 0u;
         }
         __syncthreads();
         if (!go_s) continue;
@@ -169,6 +181,7 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
         }
         __syncthreads();
         int cur = 0, nl = 0;
+        [[maybe_unused]] unsigned passed = 0u;
         for (int64_t base = r0; base < r1; base += FS_NW * RR) {
             int64_t rr[RR];
 #pragma unroll
@@ -190,8 +203,11 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
                         if (rr[i] < 0) continue;
                         double s = METRIC == METRIC_L2 ? -s4[i] : s4[i];
                         const uint32_t id = (uint32_t)rr[i];
-                        if constexpr (XF::active)
+                        if constexpr (PERQ) {
+                            if (!xf.template key<METRIC>(q, id, s, passed)) continue;
+                        } else if constexpr (XF::active) {
                             if (!xf.template key<METRIC>(id, s4[i], s)) continue;
+                        }
                         if (!full || fs_better(s, id, ts, ti)) {
                             const int slot = atomicAdd(&nb_s, 1);
                             L.bsc[slot] = s;
@@ -208,6 +224,8 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
                 __syncthreads();
             }
         }
+        if constexpr (PERQ)
+            if (lane == 0 && passed) atomicAdd(&passed_s, passed);
         // this workgroup's list -> scratch; the last workgroup of the query merges all of them
         double* gs = a.gsc + ((size_t)q * G + b) * k;
         uint32_t* gi = a.gid + ((size_t)q * G + b) * k;
@@ -217,6 +235,8 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (every storing wave, before the add)
         __syncthreads();
+        if constexpr (PERQ)
+            if (tid == 0 && passed_s) xf.count(q, passed_s);
         if (tid == 0)
             last_s = __hip_atomic_fetch_add(a.gdone + q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
                              (unsigned)(G - 1) ? 1 : 0;

@@ -1,5 +1,6 @@
 // vs_walk.h -- what the jobs built as "an exact ranking, then a device walk over it" share on the host
-// (vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip, vs_fuse_host.hip): the
+// (vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip, vs_fuse_host.hip, vs_after_host.hip; DESIGN
+// §7h-§7l): the
 // driver of tiers 1 and 2, which deepens the lists until the walk is complete, the HIP-event stopwatch and
 // the carving of a walk's output block.
 #pragma once

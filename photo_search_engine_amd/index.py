@@ -379,6 +379,50 @@ ADJUST_MODES = {"auto": 0, "direct": 1, "bound": 2, "scan": 3}  # VS_ADJUST_*
 FUSE_KINDS = {"any": 0, "all": 1}  # VS_FUSE_ANY / VS_FUSE_ALL
 FUSE_MODES = {"auto": 0, "lists": 1, "scan": 2}  # VS_FUSE_*
 FUSE_MAX_Q = 8  # VS_FUSE_MAX_Q
+AFTER_MODES = {"auto": 0, "lists": 1, "scan": 2}  # VS_AFTER_*
+
+
+def after_arrays(nq: int, after, rank_hint=None):
+    """``(after, rank_hint)`` of a paged search as contiguous int64 ``(nq,)`` arrays: ``after`` a scalar (every
+    query's cursor) or one row id per query, ``-1`` = from the top; ``rank_hint`` likewise, ``None`` = no
+    hints."""
+    out = []
+    for name, a in (("after", after), ("rank_hint", rank_hint)):
+        if a is None:
+            if name == "after":
+                raise ValueError("after must be a row id, -1, or one of either per query")
+            out.append(None)
+            continue
+        a = np.asarray(a)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"{name} must hold integers")
+        a = a.astype(np.int64)
+        if a.ndim == 0:
+            a = np.full((nq,), int(a), dtype=np.int64)
+        if a.shape != (nq,):
+            raise ValueError(f"{name} must be a scalar or {nq} values (one per query), got shape {a.shape}")
+        out.append(np.ascontiguousarray(a))
+    return out[0], out[1]
+
+
+def iter_pages(search_after, nq: int, page: int):
+    """The generator behind ``iter_search``: ``search_after(after, hint) -> (D, I, rank)`` called with each
+    page's last id as the next cursor and ``rank + returned`` as the next hint, until every query's page came
+    back short.  A query whose ranking has ended keeps its cursor (its later pages are all padding)."""
+    page = int(page)
+    if page < 1:
+        raise ValueError("page must be >= 1")
+    after = np.full((nq,), -1, dtype=np.int64)
+    hint = np.zeros((nq,), dtype=np.int64)
+    while True:
+        D, I, rank = search_after(after, hint)
+        yield D, I
+        got = (I >= 0).sum(axis=1)
+        if nq == 0 or bool(np.all(got < page)):
+            return
+        rows = np.arange(nq)
+        after = np.where(got > 0, I[rows, np.maximum(got, 1) - 1], after).astype(np.int64)
+        hint = (rank + got).astype(np.int64)
 
 
 def adjust_arrays(n: int, scale=None, bias=None):
@@ -845,6 +889,73 @@ class FlatIndex:
         check(self._L.vs_fuse_last_times(self._h, buf, 6))
         return {"search_ms": [float(buf[0]), float(buf[2])], "walk_ms": [float(buf[1]), float(buf[3])],
                 "scan_ms": float(buf[4]), "scan_walk_ms": float(buf[5])}
+
+    def search_after(self, q, k: int, after, sel=None, rank_hint=None, return_rank: bool = False):
+        """The ``k`` rows that follow a cursor row in :meth:`search`'s ranking (``vs_search_after``,
+        include/vs.h): ``after`` is a row id per query (or one for all), ``-1`` = from the top; the members
+        -- every row, under ``sel`` the rows it allows -- that rank strictly after the cursor row's position
+        (a worse score, or an equal score and a higher id) come back best first as ``(D, I)``, padded as
+        :meth:`search` pads, and with ``return_rank`` as ``(D, I, rank)``, ``rank`` the members at or before
+        the cursor.  The cursor row need not be a member.  ``rank_hint`` (the caller's guess of ``rank``,
+        ``-1`` = unknown) changes the work only, never the result."""
+        q = self._queries(q, "search_after")
+        nq, k = q.shape[0], int(k)
+        if k < 1:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "k must be >= 1")
+        after, hint = after_arrays(nq, after, rank_hint)
+        D = np.empty((nq, k), dtype=np.float32)
+        I = np.empty((nq, k), dtype=np.int64)
+        rank = np.zeros((nq,), dtype=np.int64)
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_search_after(self._h, sh, _ptr(q), nq, k, _ptr(after), None if hint is None else _ptr(hint),
+                                          _ptr(D), _ptr(I), _ptr(rank)))
+        return (D, I, rank) if return_rank else (D, I)
+
+    def iter_search(self, q, page: int, sel=None):
+        """Generator of ``(D, I)`` pages of ``page`` rows for a batch of queries: :meth:`search_after` chained
+        from the top, each page's last id the next cursor and ``rank + returned`` the next hint.  The pages of
+        a query concatenate to its whole ranking; the generator ends when every query's page came back short
+        (a query that ended earlier yields padding meanwhile).  ``sel`` (a :class:`Selector`, a mask or ids) is
+        resolved once."""
+        q = self._queries(q, "iter_search")
+        if int(page) < 1:
+            raise ValueError("page must be >= 1")
+
+        def pages():
+            with self._sel(sel) as (s, _):
+                yield from iter_pages(lambda after, hint: self.search_after(q, page, after, sel=s, rank_hint=hint,
+                                                                            return_rank=True), q.shape[0], page)
+        return pages()
+
+    def set_after_mode(self, mode: str) -> None:
+        """Force the tier of paged searches (``"lists"``, ``"scan"``) or let the library choose
+        (``"auto"``); the same bits under every mode (``vs_set_after_mode``)."""
+        if mode not in AFTER_MODES:
+            raise ValueError(f"after tier must be one of {sorted(AFTER_MODES)}")
+        check(self._L.vs_set_after_mode(self._h, AFTER_MODES[mode]))
+
+    def set_after_depth(self, first: int = 0, limit: int = 0) -> None:
+        """The list lengths :meth:`search_after` cuts: the first list and the longest one (``0`` = the
+        defaults; the same bits under every setting, ``vs_set_after_depth``)."""
+        check(self._L.vs_set_after_depth(self._h, int(first), int(limit)))
+
+    def after_last_stats(self) -> dict:
+        """The last :meth:`search_after`: queries, how many were complete after the first list, after a
+        deeper list, how many the scan answered, the longest list walked and the tier taken
+        (``vs_after_last_stats``)."""
+        buf = (ctypes.c_int64 * 6)()
+        check(self._L.vs_after_last_stats(self._h, buf, 6))
+        tier = {v: n for n, v in AFTER_MODES.items()}[int(buf[5])]
+        return {"queries": int(buf[0]), "first": int(buf[1]), "deeper": int(buf[2]), "scan": int(buf[3]),
+                "longest": int(buf[4]), "tier": tier}
+
+    def after_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`search_after`: list search and cut per list tier, the
+        cursor scoring and the scan (``vs_after_last_times``)."""
+        buf = (ctypes.c_double * 6)()
+        check(self._L.vs_after_last_times(self._h, buf, 6))
+        return {"search_ms": [float(buf[0]), float(buf[2])], "cut_ms": [float(buf[1]), float(buf[3])],
+                "score_ms": float(buf[4]), "scan_ms": float(buf[5])}
 
     def set_range_mode(self, mode: str) -> None:
         """Force the tier of range searches (``"scan"``, ``"screen"`` where it applies) or let the

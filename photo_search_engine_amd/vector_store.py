@@ -514,6 +514,69 @@ class VectorStore:
                 for distance, index, which, sub in zip(D[0].tolist(), I[0].tolist(), W[0].tolist(), U[0].tolist())
                 if index != -1]
 
+    def search_page(self, query_embedding: List[float], top_k: int, after=None, allowed=None) -> List[Dict]:
+        """:meth:`search` continued (an addition at the boundary; Elasticsearch ``search_after``, Qdrant and
+        Milvus ``offset``, Weaviate ``after``): the ``top_k`` items that follow ``after`` in the exact
+        ranking -- a "load more" page at any depth, with no ``top_k = offset + page`` re-search and no limit
+        at 3276.  ``after`` is the photo path of the last item shown, or that item's result dict from the
+        previous page (its ``"rank"`` then tells the index where the page lies); ``None`` starts from the
+        top, where the page is :meth:`search`'s.  Each result is :meth:`search`'s dict plus ``"rank"``, the
+        item's 0-based position in the ranking (among the ``allowed`` items).  The item ``after`` names need
+        not pass ``allowed``: its position in the ranking is defined either way.  Pages chained this way
+        never repeat or skip an item, ties included; a page shorter than ``top_k`` is the last.  The same
+        ``query_embedding`` and ``allowed`` must be passed on every page.  The guards, the normalisation and
+        the ``k = min(top_k, ntotal)`` clamp are :meth:`search`'s; ``allowed`` as there; a path the store does
+        not hold raises ``ValueError``.  HNSW stores answer through the exact flat path, as filtered calls
+        do."""
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        if len(query_embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
+        if not hasattr(self.index, "search_after"):
+            raise NotImplementedError("search_page needs a one-device flat index")
+        n = int(self.index.ntotal)
+        k = min(int(top_k), n)
+        cursor, hint = -1, 0
+        if after is not None:
+            path, hint = after, -1
+            if isinstance(after, dict):
+                metadata = after.get("metadata")
+                path = metadata.get("photo_path") if isinstance(metadata, dict) else None
+                if isinstance(after.get("rank"), int):
+                    hint = int(after["rank"]) + 1
+            row = self._path_to_index.get(path) if isinstance(path, str) else None
+            if row is None or row >= n:
+                raise ValueError(f"search_page: no item with photo path {path!r}")
+            cursor = int(row)
+        sel = None if allowed is None else self._allowed_rows(allowed)
+        D, I, rank = self.index.search_after(self._normalize_query(query_embedding), k, cursor, sel=sel,
+                                             rank_hint=hint, return_rank=True)
+        return [{"metadata": self.metadata[index], "distance": float(distance), "rank": int(rank[0]) + j}
+                for j, (distance, index) in enumerate(zip(D[0].tolist(), I[0].tolist())) if index != -1]
+
+    def iter_search(self, query_embedding: List[float], page_size: int, allowed=None):
+        """Generator over :meth:`search_page`: pages of ``page_size`` items from the top of the ranking until
+        it ends (the last page is the first shorter than ``page_size``; an empty store yields nothing).
+        ``allowed`` is resolved once, so a predicate runs over the metadata once, not per page."""
+        if int(page_size) < 1:
+            raise ValueError("page_size must be >= 1")
+        if self.index is None or self.index.ntotal == 0:
+            return
+        own = allowed is not None and not hasattr(allowed, "close")  # (a caller's selector stays the caller's)
+        sel = self.index.selector(self._allowed_rows(allowed)) if own else allowed
+        try:
+            after = None
+            while True:
+                page = self.search_page(query_embedding, page_size, after=after, allowed=sel)
+                if page:
+                    yield page
+                if len(page) < int(page_size):
+                    return
+                after = page[-1]
+        finally:
+            if own:
+                sel.close()
+
     def _group_keys(self, group_by, n: int):
         """``(groups, values, own)`` of a ``group_by``: the index's group keys object, the value each
         non-negative key stands for (``None``: the key itself), and whether the caller closes the object (a cached one stays)."""
