@@ -791,6 +791,74 @@ int vs_after_last_stats(vs_index* index, int64_t* out, int cap);
  * scan */
 int vs_after_last_times(vs_index* index, double* out, int cap);
 
+/* ==== facet counts =============================================================================
+ * "About 1,240 photos -- 2019 (12), 2020 (40), 2021 (7)": how many members pass a radius, and how they
+ * split over a group key, exactly, without producing, ordering or shipping a single row (Elasticsearch
+ * count + terms aggregation, Qdrant count + facet, Typesense / Meilisearch facet_by; faiss has none).
+ * vs_range_search + a host bincount answers the same question, but appends 12 bytes per passing row,
+ * sorts every segment, ships 20 bytes per result and refuses past max_total; this call moves
+ * nq x (G + 1) integers.
+ *
+ * Members: with groups, the rows the groups object covers (rows added later are no members, the rule of
+ * vs_search_groups); without groups (NULL), every stored row; with a selector (may be NULL) those of
+ * them it allows, under vs_search_sel's rules.  A stale selector, stale groups and groups of another
+ * index are VS_ERR_ARG.
+ * Predicate: vs_range_search's, exactly.  S the canonical fp64 score, D = (float)S: a member passes iff
+ * D > radius[q] (inner product) or D < radius[q] (squared L2) -- strict, on the fp32 value.
+ * Outputs, G = vs_groups_count(groups):
+ *   counts[q][g], g < G: passing members of the group with the g-th smallest non-negative key (the
+ *                        column order is vs_groups_keys');
+ *   counts[q][G]:        passing members with a negative key (ungrouped rows), together;
+ *   totals[q]:           passing members = the sum of row q of counts.
+ * Identities (tests/test_gpu_facet.py holds the call to them):
+ *   totals[q] == lims[q + 1] - lims[q] of vs_range_search under the same selector, restricted to the
+ *   covered rows; counts[q] == the bincount of the group codes over that call's I; with radius -inf
+ *   (inner product) or +inf (L2) counts[q][g] is the group's size under the selector -- the `sizes`
+ *   vs_search_groups reports; with the opposite infinity everything is 0.
+ *
+ * A NaN radius, null q, null radius, null counts with groups (or counts without groups) and both outputs
+ * null are VS_ERR_ARG before anything is launched; nq = 0 returns at once; an empty member set gives
+ * zeros.  Shared lock, one leased context, the call synchronises (the shape of vs_range_search).
+ *
+ * Tiers (the same integers under each; vs_set_range_mode applies):
+ * SCAN: every dtype and metric, any nq, with or without a selector: the range scan with a histogram in
+ * place of the pair buffer.
+ * SCREEN: bf16 / f16, blocks of 9..256 queries, no selector: the native MFMA screen started at the
+ * radius' key, then the exact refine over the survivors.  A query whose survivor list a workgroup had to
+ * cut (drop > thr0) gets its counter row zeroed on the device and is re-answered by the scan: no query
+ * is counted from a list that may be incomplete, no row is counted twice.
+ * Histogram forms of the scan (the same integers under each; vs_set_facet_hist):
+ * GLOBAL: one 64-bit device atomic per distinct bin among the rows a wave scored in one step;
+ * LDS: G + 1 uint32 bins in the workgroup's LDS behind the query, flushed per query -- the non-zero bins
+ * only -- with one device atomic each; needs G + 1 <= VS_FACET_LDS_BINS (forcing it past that is
+ * VS_ERR_ARG); AUTO: DESIGN §7m.
+ *
+ * Device memory: the counter table of one query block, nqb x (G + 1) 64-bit counters, bounded by
+ * vs_set_facet_staging_bytes (process-wide, default 64 MiB; values below one query's row of counters
+ * act as that row): a block takes min(256, bytes / (8 (G + 1))) queries, at least 1; a block of fewer
+ * than 9 takes SCAN.  The table is counted in vs_device_bytes_live and freed before the call returns.
+ *
+ * Not covered: queries taken from stored rows (VS_SELF_*); several radii per query (repeat the query);
+ * per-group best rows (vs_search_groups); sums or means of scores (they depend on summation order). */
+int vs_range_count(vs_index* index, const vs_groups* groups /* may be NULL */, const vs_sel* sel /* may be NULL */,
+                   const float* q, int64_t nq, const float* radius /* host nq */,
+                   int64_t* counts /* host nq x (G + 1); NULL iff groups is NULL */,
+                   int64_t* totals /* host nq, may be NULL */);
+/* the G distinct non-negative keys of a groups object, ascending: the columns of counts */
+int vs_groups_keys(const vs_groups* groups, int64_t* out /* host G, ascending */);
+#define VS_FACET_HIST_AUTO 0
+#define VS_FACET_HIST_LDS 1
+#define VS_FACET_HIST_GLOBAL 2
+#define VS_FACET_LDS_BINS 8192
+int vs_set_facet_hist(vs_index* index, int form);
+int vs_set_facet_staging_bytes(int64_t bytes); /* >= 1 */
+/* last call on the handle, up to cap (5): {sum of totals, tier taken (VS_RANGE_SCAN / VS_RANGE_SCREEN),
+ * queries re-answered by the scan, histogram form the scan took (0: no scan ran), query blocks} */
+int vs_facet_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/facet_timing.py): the last call on the handle, up to cap (3): ms of
+ * HIP-event time {screen + refine, scan, table readback} */
+int vs_facet_last_times(vs_index* index, double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

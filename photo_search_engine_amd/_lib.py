@@ -165,6 +165,13 @@ _SIGS = {
     "vs_set_after_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
     "vs_after_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_after_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    # facet counts
+    "vs_range_count": (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _vp]),
+    "vs_groups_keys": (ctypes.c_int, [_vp, _vp]),
+    "vs_set_facet_hist": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "vs_set_facet_staging_bytes": (ctypes.c_int, [_c_i64]),
+    "vs_facet_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_facet_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

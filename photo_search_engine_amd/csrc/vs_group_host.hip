@@ -119,13 +119,6 @@ void deliver_walk(const GrBlock& w, int64_t m, const int64_t* idx, GrOut& out) {
     }
 }
 
-void check_groups(const vs_index* ix, const vs_groups* gr) {
-    if (!gr) throw VsError(VS_ERR_ARG, "null groups");
-    if (gr->ix != ix) throw VsError(VS_ERR_ARG, "groups belong to another index");
-    if (gr->gen != ix->reset_gen.load() || gr->n_cov > ix->ntotal)
-        throw VsError(VS_ERR_ARG, "stale groups (the index was reset, or rows were removed, after they were made)");
-}
-
 // ---- tier 3: one query's restricted rounds ---------------------------------------------------------
 struct Round3 {
     vs_index* ix;
@@ -245,6 +238,14 @@ int64_t restricted_rounds(Round3& r, const float* q, int64_t qi, GrOut& out, Wal
 
 }  // namespace
 
+// (declared in vs_index.h)
+void vs::check_groups(const vs_index* ix, const vs_groups* gr) {
+    if (!gr) throw VsError(VS_ERR_ARG, "null groups");
+    if (gr->ix != ix) throw VsError(VS_ERR_ARG, "groups belong to another index");
+    if (gr->gen != ix->reset_gen.load() || gr->n_cov > ix->ntotal)
+        throw VsError(VS_ERR_ARG, "stale groups (the index was reset, or rows were removed, after they were made)");
+}
+
 extern "C" {
 
 int vs_groups_create(vs_index* ix, const int64_t* keys, int64_t n, vs_groups** out) {
@@ -319,6 +320,16 @@ void vs_groups_destroy(vs_groups* gr) {
 
 int64_t vs_groups_count(const vs_groups* gr) { return gr ? gr->G : -1; }
 int64_t vs_groups_rows(const vs_groups* gr) { return gr ? gr->n_cov : -1; }
+
+int vs_groups_keys(const vs_groups* gr, int64_t* out) {
+    return guarded([&] {
+        if (!gr) throw VsError(VS_ERR_ARG, "null groups");
+        if (gr->G == 0) return;
+        if (!out) throw VsError(VS_ERR_ARG, "null host buffer");
+        DeviceGuard dg(gr->device);
+        HIP_CHECK(hipMemcpy(out, gr->gkey.p, (size_t)gr->G * sizeof(int64_t), hipMemcpyDeviceToHost));
+    });
+}
 
 int vs_search_groups(vs_index* ix, const vs_groups* gr, const vs_sel* sel, const float* q, int64_t nq, int32_t k,
                      int32_t group_size, int64_t* keys_out, float* D, int64_t* I, int32_t* found_out, int64_t* sizes_out) {

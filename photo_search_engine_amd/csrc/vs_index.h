@@ -1,7 +1,8 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
 // vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip,
-// vs_fuse_host.hip, vs_after_host.hip; the last five share the list-deepening driver of vs_walk.h).
+// vs_fuse_host.hip, vs_after_host.hip, vs_facet_host.hip; the five before the last share the list-deepening
+// driver of vs_walk.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -185,6 +186,13 @@ struct vs_index {
     // (vs_after_last_stats) and its ms {search, cut} per list tier, cursor scoring, scan (vs_after_last_times)
     vs::WalkState af;
     std::atomic<int> after_mode{VS_AFTER_AUTO};
+    // facet counts (vs_set_facet_hist): the last call's {sum of totals, tier taken, queries re-answered by the
+    // scan, histogram form the scan took, query blocks} (vs_facet_last_stats) and its ms {screen + refine,
+    // scan, table readback} (vs_facet_last_times)
+    std::atomic<int> facet_hist{VS_FACET_HIST_AUTO};
+    std::mutex facet_mu;
+    int64_t facet_stats[5] = {0, 0, 0, 0, 0};
+    double facet_times[3] = {0, 0, 0};
     int last_kernel_kind = 0;  // 1 = mfma, 2 = gemv, 3 = int8 mfma, 4 = int8 gemv, 5 = exact full scan
     // Screen health (first passes of MFMA batches): the certificate-failure count of a batch is read
     // back without a host wait (pinned word + event, observed by a later search).  A failed query
@@ -387,6 +395,9 @@ enum : unsigned { LISTS_HOST = 1, LISTS_DEVICE = 2 };
 StagedOut exact_lists(vs_index* ix, Ctx* c, const vs_sel* sel, const SelPlan& plan, int64_t m, int kk, unsigned want,
                       hipStream_t st);
 
+// ---- vs_group_host.hip ----
+void check_groups(const vs_index* ix, const vs_groups* gr);
+
 // ---- vs_range_host.hip ----
 struct RangeStats {
     int64_t total = 0, tier = VS_RANGE_SCAN, rescanned = 0, host_sorted = 0;
@@ -399,6 +410,10 @@ struct RangeSelf {
     int64_t row0 = 0;
 };
 bool range_screen_applies(const vs_index* ix, const vs_sel* sel, int nqb);
+// the SCREEN tier's first half over one block of device queries: the native MFMA screen of every stored
+// row started at the key of radius_d[q] (device [nqb]); the survivors are in glist / gcnt of the result,
+// its drop / thr0 say which lists a workgroup had to cut
+ScreenArgs range_screen(vs_index* ix, Ctx* c, const float* qd, int nqb, const float* radius_d, hipStream_t st);
 // One block of <= MFMA_QB device queries: counts[q] = the query's result count; unless count_only,
 // its rows are appended to res (D, I, S) in query order, each query's best first.
 void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int nqb, const float* rad, bool screen,

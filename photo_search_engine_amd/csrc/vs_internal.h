@@ -549,6 +549,25 @@ struct RangeEmitArgs {
 // the lower id), longer ones as they are (the host sorts them)
 hipError_t launch_range_emit(const RangeEmitArgs& a, int nq, hipStream_t st);
 
+// ---- facet counts (vs_facet.hip) ------------------------------------------------------
+// The range scan and the range refine with a histogram in place of the pair buffer (vs_range_scan.h):
+// hist[q][bin] += 1 per member row that passes radius[q], bin = gid[row] for a grouped row, bins - 1 for
+// an ungrouped one (gid null: bins == 1, everything in bin 0).
+constexpr int FACET_LDS_BINS = VS_FACET_LDS_BINS;  // most bins of the LDS form (32 KiB of uint32)
+struct FacetArgs {
+    const int32_t* gid;        // [n_cov] group codes (vs_groups), or null
+    int64_t n_cov;             // rows at or past it are no members
+    int bins;                  // G + 1 (gid null: 1)
+    unsigned long long* hist;  // [nq][bins] (zeroed by the host)
+};
+// as launch_range_scan / launch_range_refine; of RangeArgs only corpus, d, dpad, dt, metric, n_valid, q,
+// nq, radius and go are read (self_mode must be VS_SELF_KEEP, row0 0).  lds: the LDS form, bins <=
+// FACET_LDS_BINS.  The refine's form is always the global one.
+hipError_t launch_facet_scan(const RangeArgs& a, const FacetArgs& f, bool lds, int G, int qy, const uint32_t* ids,
+                             int64_t m, hipStream_t st);
+hipError_t launch_facet_refine(const RangeArgs& a, const FacetArgs& f, const u64* glist, const int* gcnt, int lcap,
+                               int ny, hipStream_t st);
+
 // ---- queries taken from stored rows (vs_rows.hip) -----------------------------------------------
 // exact lists [nq][kk] (best first, -1 padded) -> [nq][k], k <= kk, with the entry whose id is self[q]
 // taken out and the rest moved up; a list that does not hold self[q] keeps its first k entries; slots

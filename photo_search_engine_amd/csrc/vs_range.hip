@@ -3,7 +3,9 @@
 // faiss answers "which rows score at least this well" with IndexFlat::range_search; the reference
 // product cuts a guessed top-k at score floors instead (core/searcher.py:822-843 of the reference).
 // A row belongs to query q's answer iff D = (float)S passes the radius (D > r_q inner product,
-// D < r_q squared L2), S the canonical fp64 score of exact_score_rows (vs_device.h).  Kernels:
+// D < r_q squared L2), S the canonical fp64 score of exact_score_rows (vs_device.h).  Kernels
+// (k_range_scan and k_range_refine live in vs_range_scan.h, templated on what a passing row goes into:
+// here the pair buffer, in vs_facet.hip a histogram):
 //   * k_range_scan (SCAN tier): streams like fs_scan_body -- workgroup b takes positions
 //     [n b / G, n (b + 1) / G) of the row sequence, or of a selector's ascending id list -- scores
 //     every row with exact_score_rows and tests it.  The output size is unknown, so this file takes
@@ -25,99 +27,22 @@
 //     query's offset; longer segments are copied as they are and sorted on the host.
 // Every store is bounded by a capacity the host allocated: a pair slot by cap[q], an output slot by
 // the segment lengths the host read back.  Plain vector stores and returning atomics only.
-#include "vs_scan.h"
+#include "vs_range_scan.h"
 
 namespace vs {
 
-constexpr size_t RS_QLDS_MAX = 48 * 1024;  // the fp64 query is staged in LDS up to this size
-
-__device__ __forceinline__ bool rs_pass(double S, float r, int metric) {
-    const float D = (float)S;
-    return metric == METRIC_IP ? D > r : D < r;
-}
-
-// queries taken from stored rows: may row `id` be returned to the query gathered from row `self`?
-// (mode VS_SELF_KEEP for every plain range search: always)
-__device__ __forceinline__ bool rs_self_ok(int64_t id, int64_t self, int mode) {
-    return mode == VS_SELF_DROP ? id != self : mode == VS_SELF_ABOVE ? id > self : true;
-}
-
-// lane 0 of a wave: append the passing rows among its R scored rows to query q's region
-// (SELF: the queries are stored rows; without it the self fields are not read and a plain range
-// search compiles to the code it always ran)
-template <int METRIC, int R, bool SELF>
-__device__ __forceinline__ void rs_append(const RangeArgs& a, int q, float rq, int64_t off, int64_t cap,
-                                          int64_t self, const int64_t (&rr)[R], const double (&s)[R]) {
-    unsigned pass = 0u;
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-        if (rr[i] >= 0 && (!SELF || rs_self_ok(rr[i], self, a.self_mode)) && rs_pass(s[i], rq, METRIC)) pass |= 1u << i;
-    if (!pass) return;
-    unsigned long long pos = atomicAdd(a.cnt + q, (unsigned long long)__popc(pass));
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-        if ((pass >> i) & 1u) {
-            if ((int64_t)pos < cap) {
-                a.psc[off + (int64_t)pos] = s[i];
-                a.pid[off + (int64_t)pos] = (uint32_t)rr[i];
-            }
-            ++pos;
-        }
-}
-
-template <bool QLDS>
-__device__ __forceinline__ void rs_stage_query(double* qs, const float* qv, int d, int ng) {
-    if constexpr (QLDS)
-        for (int i = threadIdx.x; i < d; i += FS_THREADS) qs[(i & 7) * ng + (i >> 3)] = (double)qv[i];
-}
-
 // ---- SCAN tier ------------------------------------------------------------------------------------
-template <int DT, int METRIC, bool QLDS, bool SEL, bool SELF>
-__global__ void __launch_bounds__(FS_THREADS) k_range_scan(RangeArgs a, const uint32_t* __restrict__ ids, int64_t m) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    double* qs = (double*)smem;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int b = blockIdx.x, G = gridDim.x;
-    const int ng = (a.d + 7) >> 3;
-    constexpr int RR = fs_rows<DT>();
-    // (a self-join under VS_SELF_ABOVE: rows below row0 pass for no query of the block)
-    const int64_t lo = SEL || !SELF ? 0 : a.row0;
-    const int64_t nseq = SEL ? m : a.n_valid - lo;
-    const int64_t r0 = lo + nseq * b / G, r1 = lo + nseq * (b + 1) / G;
-    for (int q = blockIdx.y; q < a.nq; q += gridDim.y) {
-        if (a.go && a.go[q] == 0) continue;  // (block-uniform)
-        __syncthreads();                     // (the previous query's readers of qs are done)
-        const float* qv = a.q + (int64_t)q * a.d;
-        rs_stage_query<QLDS>(qs, qv, a.d, ng);
-        __syncthreads();
-        const float rq = a.radius[q];
-        const int64_t off = a.off[q], cap = a.cap[q];
-        const int64_t self = SELF ? a.self[q] : -1;
-        for (int64_t base = r0; base < r1; base += FS_NW * RR) {
-            int64_t rr[RR];
-#pragma unroll
-            for (int i = 0; i < RR; ++i) {
-                const int64_t r = base + wid + (int64_t)i * FS_NW;
-                if constexpr (SEL) rr[i] = r < r1 ? (int64_t)ids[r] : -1;
-                else rr[i] = r < r1 ? r : -1;
-            }
-            if (rr[0] < 0) continue;  // (wave-uniform)
-            double s[RR];
-            exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
-            if (lane == 0) rs_append<METRIC, RR, SELF>(a, q, rq, off, cap, self, rr, s);
-        }
-    }
-}
-
+// (k_range_scan and k_range_refine: vs_range_scan.h, here with the pair sink)
 template <int DT, int METRIC, bool QLDS>
 static void launch_range_scan_one(const RangeArgs& a, int G, int qy, size_t lds, const uint32_t* ids, int64_t m,
                                   hipStream_t st) {
     const bool self = a.self_mode != VS_SELF_KEEP;
     const dim3 grid(G, qy), block(FS_THREADS);
-    if (ids && self) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true, true>), grid, block, lds, st, a, ids, m);
-    else if (ids) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true, false>), grid, block, lds, st, a, ids, m);
-    else if (self) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false, true>), grid, block, lds, st, a, ids, m);
-    else hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false, false>), grid, block, lds, st, a, ids, m);
+    const RsPairSink::Args sa{};
+    if (ids && self) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true, true>), grid, block, lds, st, a, ids, m, sa);
+    else if (ids) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true, false>), grid, block, lds, st, a, ids, m, sa);
+    else if (self) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false, true>), grid, block, lds, st, a, ids, m, sa);
+    else hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false, false>), grid, block, lds, st, a, ids, m, sa);
 }
 
 template <int DT>
@@ -206,53 +131,6 @@ hipError_t launch_range_thr(int metric, const float* radius, const float* qinfo,
 }
 
 // ---- SCREEN tier: exact refine of the survivors ------------------------------------------------------
-template <int DT, int METRIC, bool QLDS, bool SELF>
-__global__ void __launch_bounds__(FS_THREADS) k_range_refine(RangeArgs a, const u64* __restrict__ glist,
-                                                             const int* __restrict__ gcnt, int lcap) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    double* qs = (double*)smem;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int q = blockIdx.x;
-    const int ng = (a.d + 7) >> 3;
-    constexpr int RR = fs_rows<DT>();
-    if (a.go && a.go[q] == 0) return;
-    const int n = min(max(gcnt[q], 0), lcap);
-    const float* qv = a.q + (int64_t)q * a.d;
-    rs_stage_query<QLDS>(qs, qv, a.d, ng);
-    __syncthreads();
-    const u64* keys = glist + (size_t)q * lcap;
-    const float rq = a.radius[q];
-    const int64_t off = a.off[q], cap = a.cap[q];
-    const int64_t self = SELF ? a.self[q] : -1;
-    for (int j0 = (int)blockIdx.y * FS_NW * RR; j0 < n; j0 += (int)gridDim.y * FS_NW * RR) {
-        int64_t rr[RR];
-        int first = -1;
-#pragma unroll
-        for (int i = 0; i < RR; ++i) {
-            const int j = j0 + wid + i * FS_NW;
-            rr[i] = -1;
-            if (j < n) {
-                const u64 key = keys[j];
-                const int64_t id = (int64_t)key_id(key);
-                if (key != 0ull && id < a.n_valid) rr[i] = id;  // (never an address outside the shard)
-            }
-            if (first < 0 && rr[i] >= 0) first = i;
-        }
-        if (first < 0) continue;  // (wave-uniform)
-        if (first > 0) {          // exact_score_rows reads row[0] whatever else is absent
-#pragma unroll
-            for (int i = 1; i < RR; ++i)
-                if (i == first) {
-                    rr[0] = rr[i];
-                    rr[i] = -1;
-                }
-        }
-        double s[RR];
-        exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
-        if (lane == 0) rs_append<METRIC, RR, SELF>(a, q, rq, off, cap, self, rr, s);
-    }
-}
-
 template <int DT>
 static void launch_range_refine_dt(const RangeArgs& a, const u64* glist, const int* gcnt, int lcap, int ny,
                                    hipStream_t st) {
@@ -261,7 +139,8 @@ static void launch_range_refine_dt(const RangeArgs& a, const u64* glist, const i
     const size_t lds = qlds ? qbytes : 0;
     const dim3 grid(a.nq, ny), block(FS_THREADS);
     const bool ip = a.metric == METRIC_IP, self = a.self_mode != VS_SELF_KEEP;
-#define VS_RANGE_REFINE(M, Q, S) hipLaunchKernelGGL((k_range_refine<DT, M, Q, S>), grid, block, lds, st, a, glist, gcnt, lcap)
+    const RsPairSink::Args sa{};
+#define VS_RANGE_REFINE(M, Q, S) hipLaunchKernelGGL((k_range_refine<DT, M, Q, S>), grid, block, lds, st, a, glist, gcnt, lcap, sa)
     if (ip && qlds && self) VS_RANGE_REFINE(METRIC_IP, true, true);
     else if (ip && qlds) VS_RANGE_REFINE(METRIC_IP, true, false);
     else if (ip && self) VS_RANGE_REFINE(METRIC_IP, false, true);

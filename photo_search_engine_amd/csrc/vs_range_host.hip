@@ -27,6 +27,24 @@ bool range_screen_applies(const vs_index* ix, const vs_sel* sel, int nqb) {
     return !sel && (ix->dtype == DT_BF16 || ix->dtype == DT_F16) && nqb > GEMV_NQ_MAX && nqb <= MFMA_QB;
 }
 
+// (declared in vs_index.h)  the native MFMA screen of the stored rows as search_block launches it unseeded
+// at depth MFMA_KP_MAX (the int8 screen setting does not apply), started at the radius' key
+ScreenArgs range_screen(vs_index* ix, Ctx* c, const float* qd, int nqb, const float* radius_d, hipStream_t st) {
+    ScreenArgs s = mfma_screen_base(ix, false);
+    c->qinfo.ensure(sizeof(float) * 2 * MFMA_QB);
+    c->qtile.ensure((size_t)MFMA_QB * ix->dpad * ix->es);
+    c->thr0.ensure(sizeof(u64) * MFMA_QB);
+    mfma_workspace(c, s);
+    s.part = s.glist;
+    HIP_CHECK(launch_pack_qtile(ix->dtype, qd, nqb, ix->d, ix->dpad, c->qtile.as<uint8_t>(), c->qinfo.as<float>(),
+                                c->gcnt.as<int>(), c->drop.as<u64>(), st));
+    HIP_CHECK(launch_range_thr(ix->metric, radius_d, c->qinfo.as<float>(), qd, ix->d, nqb, xmax_of(ix), gamma_of(ix->d),
+                               c->thr0.as<u64>(), st));
+    s.thr0 = c->thr0.as<u64>();
+    HIP_CHECK(launch_screen_mfma(ix->dtype, s, c->qtile.as<uint8_t>(), nqb, st));
+    return s;
+}
+
 // (declared in vs_index.h)  self: the block's queries are stored rows (vs_rows_host.hip); the kernels
 // reject the rows it excludes before they are counted, so everything below sees the filtered answer
 void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int nqb, const float* rad, bool screen,
@@ -76,20 +94,7 @@ void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int n
     std::vector<char> need((size_t)nqb, 1);
     int64_t total2 = 0;  // pairs of the second buffer (reruns)
     if (screen) {
-        // the native MFMA screen of the stored rows as search_block launches it unseeded at depth
-        // MFMA_KP_MAX (the int8 screen setting does not apply), started at the radius' key
-        ScreenArgs s = mfma_screen_base(ix, false);
-        c->qinfo.ensure(sizeof(float) * 2 * MFMA_QB);
-        c->qtile.ensure((size_t)MFMA_QB * ix->dpad * ix->es);
-        c->thr0.ensure(sizeof(u64) * MFMA_QB);
-        mfma_workspace(c, s);
-        s.part = s.glist;
-        HIP_CHECK(launch_pack_qtile(ix->dtype, qd, nqb, ix->d, ix->dpad, c->qtile.as<uint8_t>(), c->qinfo.as<float>(),
-                                    c->gcnt.as<int>(), c->drop.as<u64>(), st));
-        HIP_CHECK(launch_range_thr(ix->metric, a.radius, c->qinfo.as<float>(), qd, ix->d, nqb, xmax_of(ix), gamma_of(ix->d),
-                                   c->thr0.as<u64>(), st));
-        s.thr0 = c->thr0.as<u64>();
-        HIP_CHECK(launch_screen_mfma(ix->dtype, s, c->qtile.as<uint8_t>(), nqb, st));
+        const ScreenArgs s = range_screen(ix, c, qd, nqb, a.radius, st);
         RangeArgs r = a;
         r.go = nullptr;
         const int ny = std::max(1, std::min(32, 2 * ix->num_cu / nqb));

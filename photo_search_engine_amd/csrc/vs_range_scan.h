@@ -1,0 +1,240 @@
+// vs_range_scan.h -- the range scan and the range refine kernels, shared by the range search
+// (vs_range.hip: passing rows appended to a pair buffer) and the facet counts (vs_facet.hip: passing rows
+// counted into a per-group histogram).  One K loop, one exact_score_rows call and one predicate; what
+// happens to a row that passes is the business of the SINK, a template parameter built from its own
+// kernel argument (SINK::Args) and the workgroup's dynamic LDS:
+//   begin(a, q)      every thread, per query: the query's state (the pair sink's region)
+//   open(tid)        every thread, per query, between the two barriers that fence the staged query
+//   put<..>(..)      lane 0 of a wave: its R scored rows
+//   close(q, tid)    every thread, after the query's last row (the next query's first barrier follows)
+// The pair sink's open / close are empty and take no barrier: a plain range search compiles to the code
+// it always ran.
+#pragma once
+#include "vs_scan.h"
+
+namespace vs {
+
+constexpr size_t RS_QLDS_MAX = 48 * 1024;  // the fp64 query is staged in LDS up to this size
+
+__device__ __forceinline__ bool rs_pass(double S, float r, int metric) {
+    const float D = (float)S;
+    return metric == METRIC_IP ? D > r : D < r;
+}
+
+// queries taken from stored rows: may row `id` be returned to the query gathered from row `self`?
+// (mode VS_SELF_KEEP for every plain range search: always)
+__device__ __forceinline__ bool rs_self_ok(int64_t id, int64_t self, int mode) {
+    return mode == VS_SELF_DROP ? id != self : mode == VS_SELF_ABOVE ? id > self : true;
+}
+
+// lane 0 of a wave: append the passing rows among its R scored rows to query q's region
+// (SELF: the queries are stored rows; without it the self fields are not read and a plain range
+// search compiles to the code it always ran)
+template <int METRIC, int R, bool SELF>
+__device__ __forceinline__ void rs_append(const RangeArgs& a, int q, float rq, int64_t off, int64_t cap,
+                                          int64_t self, const int64_t (&rr)[R], const double (&s)[R]) {
+    unsigned pass = 0u;
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+        if (rr[i] >= 0 && (!SELF || rs_self_ok(rr[i], self, a.self_mode)) && rs_pass(s[i], rq, METRIC)) pass |= 1u << i;
+    if (!pass) return;
+    unsigned long long pos = atomicAdd(a.cnt + q, (unsigned long long)__popc(pass));
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+        if ((pass >> i) & 1u) {
+            if ((int64_t)pos < cap) {
+                a.psc[off + (int64_t)pos] = s[i];
+                a.pid[off + (int64_t)pos] = (uint32_t)rr[i];
+            }
+            ++pos;
+        }
+}
+
+// the range search's sink: (S, id) pairs into the query's region of the pair buffer
+struct RsPairSink {
+    struct Args {};
+    __device__ __forceinline__ RsPairSink(const Args&, uint8_t*) {}
+    struct Q {
+        int64_t off, cap;
+    };
+    __device__ __forceinline__ Q begin(const RangeArgs& a, int q) const { return {a.off[q], a.cap[q]}; }
+    __device__ __forceinline__ void open(int) const {}
+    template <int METRIC, int R, bool SELF>
+    __device__ __forceinline__ void put(const RangeArgs& a, int q, float rq, const Q& st, int64_t self,
+                                        const int64_t (&rr)[R], const double (&s)[R]) const {
+        rs_append<METRIC, R, SELF>(a, q, rq, st.off, st.cap, self, rr, s);
+    }
+    __device__ __forceinline__ void close(int, int) const {}
+};
+
+// the facet counts' sink: hist[q][bin] += 1 per passing member, bin = the row's group code, or G for an
+// ungrouped row (gid null: the one bin 0).  Rows at or past n_cov are no members (a selector made after
+// the groups allows them; the screen lists them).  LDS = false: one device atomic per distinct bin among
+// the wave-step's R rows.  LDS = true: the workgroup's own uint32 bins (a workgroup scores fewer than
+// 2^31 rows per query), zeroed in open(), flushed in close() -- the non-zero ones -- with one device
+// atomic each.  Every index is below `bins`, the row length the host sized hist by.
+template <bool LDS>
+struct RsCountSink {
+    struct Args {
+        FacetArgs f;
+        int bins_off;  // LDS form: the bins' byte offset in dynamic LDS (behind the staged query)
+    };
+    FacetArgs f;
+    unsigned* lbins;  // LDS form: [bins]
+    __device__ __forceinline__ RsCountSink(const Args& sa, uint8_t* smem)
+        : f(sa.f), lbins((unsigned*)(smem + sa.bins_off)) {}
+    struct Q {};
+    __device__ __forceinline__ Q begin(const RangeArgs&, int) const { return {}; }
+    __device__ __forceinline__ void open(int tid) const {
+        if constexpr (LDS)
+            for (int b = tid; b < f.bins; b += FS_THREADS) lbins[b] = 0u;
+    }
+    template <int METRIC, int R, bool SELF>
+    __device__ __forceinline__ void put(const RangeArgs&, int q, float rq, const Q&, int64_t, const int64_t (&rr)[R],
+                                        const double (&s)[R]) const {
+        static_assert(!SELF, "facet counts take no queries from stored rows");
+        unsigned pass = 0u;
+        int bin[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            bin[i] = 0;
+            if (rr[i] >= 0 && rr[i] < f.n_cov && rs_pass(s[i], rq, METRIC)) {
+                pass |= 1u << i;
+                if (f.gid) {
+                    const int c = f.gid[rr[i]];
+                    bin[i] = c >= 0 && c < f.bins - 1 ? c : f.bins - 1;
+                }
+            }
+        }
+        if (!pass) return;
+        if constexpr (LDS) {
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+                if ((pass >> i) & 1u) atomicAdd(lbins + bin[i], 1u);
+        } else {
+            unsigned long long* row = f.hist + (int64_t)q * f.bins;
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+                if ((pass >> i) & 1u) {
+                    unsigned n = 1u;
+#pragma unroll
+                    for (int j = i + 1; j < R; ++j)
+                        if (((pass >> j) & 1u) && bin[j] == bin[i]) {
+                            ++n;
+                            pass &= ~(1u << j);
+                        }
+                    atomicAdd(row + bin[i], (unsigned long long)n);
+                }
+        }
+    }
+    __device__ __forceinline__ void close(int q, int tid) const {
+        if constexpr (LDS) {
+            __syncthreads();  // (every wave's adds of this query are in)
+            unsigned long long* row = f.hist + (int64_t)q * f.bins;
+            for (int b = tid; b < f.bins; b += FS_THREADS) {
+                const unsigned v = lbins[b];
+                if (v) atomicAdd(row + b, (unsigned long long)v);
+            }
+        }
+    }
+};
+
+template <bool QLDS>
+__device__ __forceinline__ void rs_stage_query(double* qs, const float* qv, int d, int ng) {
+    if constexpr (QLDS)
+        for (int i = threadIdx.x; i < d; i += FS_THREADS) qs[(i & 7) * ng + (i >> 3)] = (double)qv[i];
+}
+
+// ---- SCAN tier ------------------------------------------------------------------------------------
+template <int DT, int METRIC, bool QLDS, bool SEL, bool SELF, class SINK = RsPairSink>
+__global__ void __launch_bounds__(FS_THREADS) k_range_scan(RangeArgs a, const uint32_t* __restrict__ ids, int64_t m,
+                                                           typename SINK::Args sa) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    double* qs = (double*)smem;
+    const SINK sink(sa, smem);
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x, G = gridDim.x;
+    const int ng = (a.d + 7) >> 3;
+    constexpr int RR = fs_rows<DT>();
+    // (a self-join under VS_SELF_ABOVE: rows below row0 pass for no query of the block)
+    const int64_t lo = SEL || !SELF ? 0 : a.row0;
+    const int64_t nseq = SEL ? m : a.n_valid - lo;
+    const int64_t r0 = lo + nseq * b / G, r1 = lo + nseq * (b + 1) / G;
+    for (int q = blockIdx.y; q < a.nq; q += gridDim.y) {
+        if (a.go && a.go[q] == 0) continue;  // (block-uniform)
+        __syncthreads();                     // (the previous query's readers of qs are done)
+        const float* qv = a.q + (int64_t)q * a.d;
+        rs_stage_query<QLDS>(qs, qv, a.d, ng);
+        sink.open(tid);
+        __syncthreads();
+        const float rq = a.radius[q];
+        const typename SINK::Q sq = sink.begin(a, q);
+        const int64_t self = SELF ? a.self[q] : -1;
+        for (int64_t base = r0; base < r1; base += FS_NW * RR) {
+            int64_t rr[RR];
+#pragma unroll
+            for (int i = 0; i < RR; ++i) {
+                const int64_t r = base + wid + (int64_t)i * FS_NW;
+                if constexpr (SEL) rr[i] = r < r1 ? (int64_t)ids[r] : -1;
+                else rr[i] = r < r1 ? r : -1;
+            }
+            if (rr[0] < 0) continue;  // (wave-uniform)
+            double s[RR];
+            exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
+            if (lane == 0) sink.template put<METRIC, RR, SELF>(a, q, rq, sq, self, rr, s);
+        }
+        sink.close(q, tid);
+    }
+}
+
+// ---- SCREEN tier: exact refine of the survivors ------------------------------------------------------
+template <int DT, int METRIC, bool QLDS, bool SELF, class SINK = RsPairSink>
+__global__ void __launch_bounds__(FS_THREADS) k_range_refine(RangeArgs a, const u64* __restrict__ glist,
+                                                             const int* __restrict__ gcnt, int lcap,
+                                                             typename SINK::Args sa) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    double* qs = (double*)smem;
+    const SINK sink(sa, smem);
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int q = blockIdx.x;
+    const int ng = (a.d + 7) >> 3;
+    constexpr int RR = fs_rows<DT>();
+    if (a.go && a.go[q] == 0) return;
+    const int n = min(max(gcnt[q], 0), lcap);
+    const float* qv = a.q + (int64_t)q * a.d;
+    rs_stage_query<QLDS>(qs, qv, a.d, ng);
+    __syncthreads();
+    const u64* keys = glist + (size_t)q * lcap;
+    const float rq = a.radius[q];
+    const typename SINK::Q sq = sink.begin(a, q);
+    const int64_t self = SELF ? a.self[q] : -1;
+    for (int j0 = (int)blockIdx.y * FS_NW * RR; j0 < n; j0 += (int)gridDim.y * FS_NW * RR) {
+        int64_t rr[RR];
+        int first = -1;
+#pragma unroll
+        for (int i = 0; i < RR; ++i) {
+            const int j = j0 + wid + i * FS_NW;
+            rr[i] = -1;
+            if (j < n) {
+                const u64 key = keys[j];
+                const int64_t id = (int64_t)key_id(key);
+                if (key != 0ull && id < a.n_valid) rr[i] = id;  // (never an address outside the shard)
+            }
+            if (first < 0 && rr[i] >= 0) first = i;
+        }
+        if (first < 0) continue;  // (wave-uniform)
+        if (first > 0) {          // exact_score_rows reads row[0] whatever else is absent
+#pragma unroll
+            for (int i = 1; i < RR; ++i)
+                if (i == first) {
+                    rr[0] = rr[i];
+                    rr[i] = -1;
+                }
+        }
+        double s[RR];
+        exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
+        if (lane == 0) sink.template put<METRIC, RR, SELF>(a, q, rq, sq, self, rr, s);
+    }
+}
+
+}  // namespace vs

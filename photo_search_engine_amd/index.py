@@ -363,6 +363,16 @@ class Groups:
         """Rows covered."""
         return int(self._L.vs_groups_rows(self._h))
 
+    @property
+    def keys(self) -> np.ndarray:
+        """The distinct non-negative keys, ascending int64: the columns of :meth:`FlatIndex.range_count`
+        (``vs_groups_keys``)."""
+        if self._h is None:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "groups are closed")
+        out = np.empty((self.count,), dtype=np.int64)
+        check(self._L.vs_groups_keys(self._h, _ptr(out) if out.size else None))
+        return out
+
     def close(self) -> None:
         if self._h is not None and self._h.value:
             self._L.vs_groups_destroy(self._h)
@@ -373,6 +383,11 @@ class Groups:
             self.close()
         except Exception:
             pass
+
+
+FACET_HIST = {"auto": 0, "lds": 1, "global": 2}  # VS_FACET_HIST_*
+FACET_LDS_BINS = 8192  # VS_FACET_LDS_BINS
+FACET_STAGING_DEFAULT = 64 << 20
 
 
 ADJUST_MODES = {"auto": 0, "direct": 1, "bound": 2, "scan": 3}  # VS_ADJUST_*
@@ -972,6 +987,55 @@ class FlatIndex:
         return {"total": int(buf[0]), "tier": {1: "scan", 2: "screen"}.get(int(buf[1]), "none"),
                 "rescanned": int(buf[2]), "host_sorted": int(buf[3])}
 
+    def range_count(self, q, radius, groups: Optional[Groups] = None, sel=None):
+        """Exact facet counts (``vs_range_count``, include/vs.h): how many members pass ``radius`` --
+        :meth:`range_search`'s predicate, ``radius`` a scalar or one value per query -- and how they split
+        over the groups, without producing a row.  Members: the rows ``groups`` covers (every stored row
+        without ``groups``), under ``sel`` (as in :meth:`search`) those of them it allows.  Returns
+        ``(totals, counts)``: ``totals`` int64 ``(nq,)``; ``counts`` int64 ``(nq, G + 1)`` -- column ``g``
+        the group with key ``groups.keys[g]``, the last column the rows with a negative key -- or ``None``
+        without ``groups``."""
+        q = self._queries(q, "range_count")
+        nq = q.shape[0]
+        r = range_radius(radius, nq)
+        if groups is not None and not isinstance(groups, Groups):
+            raise TypeError("groups must be a Groups object (FlatIndex.group_keys)")
+        totals = np.zeros((nq,), dtype=np.int64)
+        with self._sel(sel) as (_, sh):
+            if groups is None:
+                check(self._L.vs_range_count(self._h, None, sh, _ptr(q), nq, _ptr(r), None, _ptr(totals)))
+                return totals, None
+            if groups._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "groups are closed")
+            counts = np.zeros((nq, groups.count + 1), dtype=np.int64)
+            check(self._L.vs_range_count(self._h, groups._h, sh, _ptr(q), nq, _ptr(r), _ptr(counts), _ptr(totals)))
+        return totals, counts
+
+    def set_facet_hist(self, form: str) -> None:
+        """Force the histogram form of :meth:`range_count`'s scan (``"lds"``, ``"global"``) or let the
+        library choose (``"auto"``); the same integers under every form (``vs_set_facet_hist``).  Forcing
+        ``"lds"`` makes a call with more than ``FACET_LDS_BINS`` bins an argument error."""
+        if form not in FACET_HIST:
+            raise ValueError(f"unknown facet histogram form {form!r}")
+        check(self._L.vs_set_facet_hist(self._h, FACET_HIST[form]))
+
+    def facet_last_stats(self) -> dict:
+        """The last :meth:`range_count`: the sum of its totals, the tier taken, the queries the scan
+        re-answered after a screen overflow, the histogram form the scan took and the query blocks
+        (``vs_facet_last_stats``)."""
+        buf = (ctypes.c_int64 * 5)()
+        check(self._L.vs_facet_last_stats(self._h, buf, 5))
+        return {"total": int(buf[0]), "tier": {1: "scan", 2: "screen"}.get(int(buf[1]), "none"),
+                "rescanned": int(buf[2]), "hist": {1: "lds", 2: "global"}.get(int(buf[3]), "none"),
+                "blocks": int(buf[4])}
+
+    def facet_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`range_count`: screen + refine, scan, table readback
+        (``vs_facet_last_times``)."""
+        buf = (ctypes.c_double * 3)()
+        check(self._L.vs_facet_last_times(self._h, buf, 3))
+        return {"screen_ms": float(buf[0]), "scan_ms": float(buf[1]), "readback_ms": float(buf[2])}
+
     def selector(self, allowed) -> Selector:
         """A reusable :class:`Selector` over the rows present now (mask or ids, ``pack_allowed``)."""
         return Selector(self, allowed)
@@ -1290,6 +1354,15 @@ def set_remove_staging_bytes(nbytes: int = REMOVE_STAGING_DEFAULT) -> None:
 KMEANS_STAGING_DEFAULT = 256 << 20
 
 
+def set_facet_staging_bytes(nbytes: int = FACET_STAGING_DEFAULT) -> None:
+    """Bound, process-wide, of the counter table one query block of :meth:`FlatIndex.range_count` keeps on
+    the device (``vs_set_facet_staging_bytes``; below one query's row of counters it acts as that row)."""
+    nbytes = int(nbytes)
+    if nbytes < 1:
+        raise ValueError("facet staging bytes must be >= 1")
+    check(_lib.load().vs_set_facet_staging_bytes(nbytes))
+
+
 def set_kmeans_staging_bytes(nbytes: int = KMEANS_STAGING_DEFAULT) -> None:
     """Bytes of gathered fp32 queries a ``kmeans`` / ``assign_rows`` call may hold at once, process-wide
     (include/vs.h ``vs_set_kmeans_staging_bytes``): any value from 1 up, floored at one 256-row block.
@@ -1541,6 +1614,29 @@ class MultiDeviceFlatIndex:
                 mask &= np.unpackbits(pack_allowed(n, s), bitorder="little")[:n].astype(bool)
             s = mask
         return copy.search_groups(q, k, groups.on(copy), group_size, s)
+
+    def range_count(self, q, radius, groups: Optional[HostGroups] = None, sel=None):
+        """:meth:`FlatIndex.range_count` on the one-device copy of the rows (as :meth:`search_groups`);
+        ``sel``: a boolean mask, ids or a :class:`MaskSelector`.  The columns of ``counts`` are the
+        ascending distinct non-negative keys of ``groups``, then the ungrouped rows."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"range_count expects an (nq, {self.d}) array, got {q.shape}")
+        r = range_radius(radius, q.shape[0])
+        if groups is not None and not isinstance(groups, HostGroups):
+            raise TypeError("groups must come from this index's group_keys")
+        n = self.ntotal
+        if groups is not None and groups.n > n:
+            raise _lib.VsError(_lib.VS_ERR_ARG, "stale groups (rows were removed after they were made)")
+        copy = self._one_device_copy()
+        s = self._copy_sel(sel)
+        if groups is not None and groups.n < n:  # rows added behind the groups are no members
+            mask = np.zeros((n,), dtype=bool)
+            mask[:groups.n] = True
+            if s is not None:
+                mask &= np.unpackbits(pack_allowed(n, s), bitorder="little")[:n].astype(bool)
+            s = mask
+        return copy.range_count(q, r, None if groups is None else groups.on(copy), s)
 
     def _copy_sel(self, sel):
         """A filter of this index as one over its one-device copy (rows added after a

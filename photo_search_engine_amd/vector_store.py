@@ -639,6 +639,51 @@ class VectorStore:
         return [{"metadata": self.metadata[index], "distance": float(distance)}
                 for distance, index in zip(distances[:n].tolist(), indices[:n].tolist())]
 
+    def count_matches(self, query_embedding: List[float], threshold: float, allowed=None) -> int:
+        """How many items :meth:`search_range` would return for ``radius = threshold`` -- "about 1,240
+        photos" -- without producing one of them (an addition at the boundary; Elasticsearch's count API,
+        Qdrant ``count``).  The reference derives such figures from its over-fetched ``candidate_k`` rows
+        (core/searcher.py:627-770); this count is exact over every item.  The guards, the normalisation and
+        ``allowed`` are :meth:`search_range`'s."""
+        if self.index is None or self.index.ntotal == 0:
+            return 0
+        if len(query_embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
+        sel = None if allowed is None else self._allowed_rows(allowed)
+        totals, _ = self.index.range_count(self._normalize_query(query_embedding), float(threshold), sel=sel)
+        return int(totals[0])
+
+    def facet_counts(self, query_embedding: List[float], threshold: float, group_by, allowed=None) -> Dict[str, Any]:
+        """How the items :meth:`search_range` would return for ``radius = threshold`` split over a key --
+        "2019 (12) · 2020 (40) · 2021 (7)" -- exactly, without producing one of them (an addition at the
+        boundary; Elasticsearch ``terms`` aggregations, Qdrant's facet API, Typesense / Meilisearch
+        ``facet_by``): ``{"total": n, "counts": {value: n, ...}, "ungrouped": n}``.  ``counts`` holds only
+        the values with ``n > 0``, in ascending key order (a field's or a callable's values are keyed in
+        order of first appearance, integer keys by themselves); ``ungrouped`` counts the matching items
+        without the field.  ``group_by`` and its cache are :meth:`search_grouped`'s; ``threshold``,
+        ``allowed``, the guards and the normalisation are :meth:`search_range`'s."""
+        if self.index is None or self.index.ntotal == 0:
+            return {"total": 0, "counts": {}, "ungrouped": 0}
+        if len(query_embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
+        n = int(self.index.ntotal)
+        groups, values, own = self._group_keys(group_by, n)
+        try:
+            sel = None if allowed is None else self._allowed_rows(allowed)
+            totals, counts = self.index.range_count(self._normalize_query(query_embedding), float(threshold),
+                                                    groups=groups, sel=sel)
+        finally:
+            if own:
+                groups.close()
+        if values is None:  # integer keys: the columns are the distinct non-negative ones, ascending
+            given = np.asarray(group_by)
+            cols = np.unique(given[given >= 0]).tolist()
+        else:
+            cols = values
+        row = counts[0]
+        return {"total": int(totals[0]), "counts": {cols[g]: int(row[g]) for g in range(len(cols)) if row[g] > 0},
+                "ungrouped": int(row[len(cols)])}
+
     def search_similar(self, photo_path: str, top_k: int, allowed=None) -> List[Dict]:
         """The ``top_k`` items most similar to a photo the store holds, the photo itself left out (an
         addition at the boundary): :meth:`search`'s result dicts for the stored row of ``photo_path``
