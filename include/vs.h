@@ -859,6 +859,66 @@ int vs_facet_last_stats(vs_index* index, int64_t* out, int cap);
  * HIP-event time {screen + refine, scan, table readback} */
 int vs_facet_last_times(vs_index* index, double* out, int cap);
 
+/* ==== duplicate groups =========================================================================
+ * "Which photos are the same shot" -- bursts, re-imports, edited copies -- asks for one label per row: the
+ * connected components of "within a radius of each other" (DBSCAN with min_samples = 1, single linkage cut
+ * at a radius, the duplicate-cluster step of every deduplication pipeline; faiss has none).
+ * vs_range_search_rows(VS_SELF_ABOVE) + a host union-find answers the same question, but a burst of b
+ * frames is b (b - 1) / 2 pairs: 12 bytes each in HBM, a sort of every segment, 20 bytes each over PCIe
+ * and a refusal past max_total.  This call unites on the device and moves ntotal integers.
+ *
+ * Members: every stored row, or with a selector (may be NULL) the rows it allows, under vs_search_sel's
+ * rules: a stale selector is VS_ERR_ARG, rows added after the selector was made are no members.
+ * Edge: members a < b are joined iff vs_range_search_rows(ids = {a}, radius, VS_SELF_ABOVE) under the
+ * same selector returns b: S the canonical fp64 score of the two stored values, D = (float)S, and the edge
+ * is there iff D > radius (inner product) or D < radius (squared L2) -- strict, on the fp32 value; the
+ * predicate of VectorStore.find_duplicates and vs_search_diverse, bit for bit.  One scalar radius: a
+ * radius per row would make the relation asymmetric.  A row that is no member carries no edge: a - x - b
+ * with x not allowed does not join a and b.
+ * Outputs:
+ *   labels[i]      the smallest id of the component member i belongs to (a member with no near member is
+ *                  its own label); -1 for a row that is no member;
+ *   *n_components  distinct non-negative labels, singletons included;
+ *   *n_edges       edges, = lims[n] of the VS_SELF_ABOVE self-join over the members.
+ * The result is a pure function of the stored rows, the selector and the radius: it does not depend on
+ * the tier, the grid or the order in which the device unites.
+ * Identities (tests/test_gpu_components.py holds the call to them):
+ *   the labels are the components of the pair list of vs_range_search_rows(ids NULL | the allowed ids,
+ *   sel, VS_SELF_ABOVE), and n_edges is that call's total; radius -inf (inner product) / +inf (L2) gives
+ *   one component -- every member labelled with the lowest member id -- and m (m - 1) / 2 edges for m
+ *   members; the opposite infinity gives every member its own label and 0 edges; vs_groups_create(labels)
+ *   on an unfiltered result has vs_groups_count == *n_components (the labels are valid keys for
+ *   vs_search_groups -- "one result per burst" -- and vs_range_count -- "matches per burst").
+ *
+ * A NaN radius, null labels with ntotal > 0 and a stale selector are VS_ERR_ARG before anything is
+ * launched; an empty index returns at once with both counts 0; a selector that allows nothing gives all
+ * -1 and both counts 0.  There is no max_total: nothing grows with the number of pairs.
+ * Shared lock, one leased context, the call synchronises (the shape of vs_range_count).
+ *
+ * Tiers (the same labels and counts under each; vs_set_range_mode applies).  The members in ascending id
+ * are the queries, in blocks of 256, gathered on the device from their own rows.
+ * SCAN: every dtype and metric, with or without a selector: the range scan over the rows at or above the
+ * block's first member (with a selector: over the tail of its id list from the block's first position).
+ * SCREEN: bf16 / f16, blocks of 9..256 queries, no selector: the native MFMA screen started at the
+ * radius' key, then the exact refine over the survivors.  A query whose survivor list a workgroup had to
+ * cut (drop > thr0) gets its edge counter zeroed and is re-answered by the scan; the unions its refine
+ * made stay, since uniting a joined pair again changes nothing.
+ *
+ * Device memory: the parent array (4 bytes per row), the per-block edge counters (2 KiB per block) and the
+ * device labels (8 bytes per row), counted in vs_device_bytes_live and freed before the call returns.
+ *
+ * Not covered: vs_multi_* across shards (components need the edges between shards); neighbour counts per
+ * row; core-point DBSCAN (min_samples > 1); a screen for f32 stores. */
+int vs_range_components(vs_index* index, const vs_sel* sel /* may be NULL */, float radius,
+                        int64_t* labels /* host ntotal */, int64_t* n_components /* may be NULL */,
+                        int64_t* n_edges /* may be NULL */);
+/* last call on the handle, up to cap (6): {members, edges, components, tier taken (VS_RANGE_SCAN /
+ * VS_RANGE_SCREEN), queries re-answered by the scan after a screen overflow, query blocks} */
+int vs_components_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/components_timing.py): the last call on the handle, up to cap (3): ms of
+ * HIP-event time {gather + screen + refine, scan, flatten + readback} */
+int vs_components_last_times(vs_index* index, double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

@@ -172,6 +172,10 @@ _SIGS = {
     "vs_set_facet_staging_bytes": (ctypes.c_int, [_c_i64]),
     "vs_facet_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_facet_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    # duplicate groups
+    "vs_range_components": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _vp, _vp, _vp]),
+    "vs_components_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_components_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

@@ -568,6 +568,22 @@ hipError_t launch_facet_scan(const RangeArgs& a, const FacetArgs& f, bool lds, i
 hipError_t launch_facet_refine(const RangeArgs& a, const FacetArgs& f, const u64* glist, const int* gcnt, int lcap,
                                int ny, hipStream_t st);
 
+// ---- duplicate groups (vs_components.hip) ---------------------------------------------
+// The range scan and the range refine with a union-find in place of the pair buffer (vs_range_scan.h):
+// every passing row of query q -- a stored row, self[q], under VS_SELF_ABOVE -- is an edge: cnt[q] += 1
+// and the two rows' trees in parent[0, n_valid) are joined, the larger root under the smaller.
+hipError_t launch_cc_init(uint32_t* parent, int64_t n, hipStream_t st);  // parent[i] = i
+// as launch_range_scan / launch_range_refine; of RangeArgs corpus, d, dpad, dt, metric, n_valid, q, nq,
+// radius, go, cnt, self and row0 are read (self_mode must be VS_SELF_ABOVE)
+hipError_t launch_cc_scan(const RangeArgs& a, uint32_t* parent, int G, int qy, const uint32_t* ids, int64_t m,
+                          hipStream_t st);
+hipError_t launch_cc_refine(const RangeArgs& a, uint32_t* parent, const u64* glist, const int* gcnt, int lcap, int ny,
+                            hipStream_t st);
+// labels[id] = the root of id's tree for the m members: rows sel_ids[0, m) (ascending, each < n), or with
+// sel_ids null rows 0..m-1; the caller fills labels[0, n) with -1 first
+hipError_t launch_cc_labels(uint32_t* parent, const uint32_t* sel_ids, int64_t m, int64_t n, int64_t* labels,
+                            hipStream_t st);
+
 // ---- queries taken from stored rows (vs_rows.hip) -----------------------------------------------
 // exact lists [nq][kk] (best first, -1 padded) -> [nq][k], k <= kk, with the entry whose id is self[q]
 // taken out and the rest moved up; a list that does not hold self[q] keeps its first k entries; slots

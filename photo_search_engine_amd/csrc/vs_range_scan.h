@@ -1,6 +1,7 @@
 // vs_range_scan.h -- the range scan and the range refine kernels, shared by the range search
-// (vs_range.hip: passing rows appended to a pair buffer) and the facet counts (vs_facet.hip: passing rows
-// counted into a per-group histogram).  One K loop, one exact_score_rows call and one predicate; what
+// (vs_range.hip: passing rows appended to a pair buffer), the facet counts (vs_facet.hip: passing rows
+// counted into a per-group histogram) and the duplicate groups (vs_components.hip: passing rows united with
+// the query's own row in a union-find).  One K loop, one exact_score_rows call and one predicate; what
 // happens to a row that passes is the business of the SINK, a template parameter built from its own
 // kernel argument (SINK::Args) and the workgroup's dynamic LDS:
 //   begin(a, q)      every thread, per query: the query's state (the pair sink's region)
@@ -137,6 +138,88 @@ struct RsCountSink {
             }
         }
     }
+};
+
+// ---- duplicate groups: lock-free union-find over parent[0, n) (vs_components.hip) -----
+// Every access to `parent` while unions run is a relaxed agent-scope atomic: the array is its own and only
+// payload, so no ordering against other memory is needed, only that each word is read and written whole
+// and past this CU's L1.
+__device__ __forceinline__ uint32_t cc_load(const uint32_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the root of x's tree.  Follows parent until parent[r] == r; with HALVE, points the nodes of the path at
+// their grandparents on the way -- a value this thread has read as an ancestor of that node, hence smaller
+// than the node and an ancestor of it for ever (trees only ever merge at their roots).  A store goes to a
+// non-root only (its parent was read as another node, and a non-root never becomes a root again), so it
+// never meets a CAS that hooks a root.
+template <bool HALVE>
+__device__ __forceinline__ uint32_t cc_find(uint32_t* parent, uint32_t x) {
+    uint32_t p = cc_load(parent + x);
+    while (p != x) {
+        const uint32_t g = cc_load(parent + p);
+        if (HALVE && g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = p;
+        p = g;
+    }
+    return x;
+}
+
+// Join the trees of x and y.
+// Invariant: parent[v] <= v for every v, with equality exactly at roots.  k_cc_init sets parent[v] = v;
+// path halving stores an ancestor, which is smaller; a hook stores the smaller of two distinct roots under
+// the larger.  A path therefore descends strictly and ends, and the root of a tree is its minimum id:
+// once all edges are in, find(v) is the smallest id of v's component whatever order the unions took --
+// the labels do not depend on the schedule, the tier or the grid.
+// Hook: roots hi > lo are joined by atomicCAS(parent + hi, hi, lo), which succeeds only while hi still is
+// a root, so a root is hooked once and no union is lost.  lo needs no check: were it hooked meanwhile (or
+// read from a stale line), hi hangs under a former root of the same tree that x and y now share.  On
+// failure the CAS returns hi's new parent, an ancestor smaller than hi: the search goes on from there, so
+// every failed round strictly lowers the pair and the loop ends (at the latest with both at the tree's
+// minimum, where the roots are equal and nothing is left to do).  Uniting a joined pair again changes
+// nothing: unions are idempotent.
+__device__ __forceinline__ void cc_unite(uint32_t* parent, uint32_t x, uint32_t y) {
+    uint32_t a = cc_find<true>(parent, x), b = cc_find<true>(parent, y);
+    while (a != b) {
+        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        const uint32_t old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) return;
+        a = cc_find<true>(parent, old);
+        b = cc_find<true>(parent, lo);
+    }
+}
+
+// the duplicate groups' sink (queries are stored rows under VS_SELF_ABOVE): a passing row is an edge
+// (self, id) -- counted into the block's cnt[q] with one atomic per wave-step, and united with the query's
+// own row.  The test is the pair sink's; ids index parent[0, n_valid) only (the scan's rows and a
+// selector's ids are below n_valid, the refine drops keys at or past it, the self ids are member ids; put()
+// bounds both again).
+struct RsUnionSink {
+    struct Args {
+        uint32_t* parent;  // [n_valid]
+    };
+    uint32_t* parent;
+    __device__ __forceinline__ RsUnionSink(const Args& sa, uint8_t*) : parent(sa.parent) {}
+    struct Q {};
+    __device__ __forceinline__ Q begin(const RangeArgs&, int) const { return {}; }
+    __device__ __forceinline__ void open(int) const {}
+    template <int METRIC, int R, bool SELF>
+    __device__ __forceinline__ void put(const RangeArgs& a, int q, float rq, const Q&, int64_t self,
+                                        const int64_t (&rr)[R], const double (&s)[R]) const {
+        static_assert(SELF, "duplicate groups take their queries from stored rows");
+        if (self < 0 || self >= a.n_valid) return;
+        unsigned pass = 0u;
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (rr[i] >= 0 && rr[i] < a.n_valid && rs_self_ok(rr[i], self, a.self_mode) && rs_pass(s[i], rq, METRIC))
+                pass |= 1u << i;
+        if (!pass) return;
+        atomicAdd(a.cnt + q, (unsigned long long)__popc(pass));
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if ((pass >> i) & 1u) cc_unite(parent, (uint32_t)self, (uint32_t)rr[i]);
+    }
+    __device__ __forceinline__ void close(int, int) const {}
 };
 
 template <bool QLDS>

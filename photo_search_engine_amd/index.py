@@ -1036,6 +1036,38 @@ class FlatIndex:
         check(self._L.vs_facet_last_times(self._h, buf, 3))
         return {"screen_ms": float(buf[0]), "scan_ms": float(buf[1]), "readback_ms": float(buf[2])}
 
+    def range_components(self, radius, sel=None):
+        """Exact duplicate groups (``vs_range_components``, include/vs.h): the connected components of "within
+        ``radius`` of each other" -- :meth:`range_search_rows`' predicate under ``self_mode="above"`` -- over
+        the members: every stored row, under ``sel`` (as in :meth:`search`) the rows it allows.  Returns
+        ``(labels, n_components, n_edges)``: ``labels`` int64 ``(ntotal,)``, a member's label the smallest id
+        of its component and ``-1`` for a row that is no member; ``n_components`` counts singletons too;
+        ``n_edges`` is the self-join's pair count.  Nothing grows with the number of pairs.  The labels of
+        an unfiltered call are valid keys for :meth:`group_keys`."""
+        r = float(range_radius(radius, 1)[0])  # (one scalar; NaN raises ValueError)
+        labels = np.full((self.ntotal,), -1, dtype=np.int64)
+        nc, ne = ctypes.c_int64(0), ctypes.c_int64(0)
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_range_components(self._h, sh, r, _ptr(labels) if labels.shape[0] else None,
+                                              ctypes.byref(nc), ctypes.byref(ne)))
+        return labels, int(nc.value), int(ne.value)
+
+    def components_last_stats(self) -> dict:
+        """The last :meth:`range_components`: members, edges, components, the tier taken, the queries the
+        scan re-answered after a screen overflow and the query blocks (``vs_components_last_stats``)."""
+        buf = (ctypes.c_int64 * 6)()
+        check(self._L.vs_components_last_stats(self._h, buf, 6))
+        return {"members": int(buf[0]), "edges": int(buf[1]), "components": int(buf[2]),
+                "tier": {1: "scan", 2: "screen"}.get(int(buf[3]), "none"), "rescanned": int(buf[4]),
+                "blocks": int(buf[5])}
+
+    def components_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`range_components`: gather + screen + refine, scan,
+        flatten + readback (``vs_components_last_times``)."""
+        buf = (ctypes.c_double * 3)()
+        check(self._L.vs_components_last_times(self._h, buf, 3))
+        return {"screen_ms": float(buf[0]), "scan_ms": float(buf[1]), "readback_ms": float(buf[2])}
+
     def selector(self, allowed) -> Selector:
         """A reusable :class:`Selector` over the rows present now (mask or ids, ``pack_allowed``)."""
         return Selector(self, allowed)
@@ -1637,6 +1669,15 @@ class MultiDeviceFlatIndex:
                 mask &= np.unpackbits(pack_allowed(n, s), bitorder="little")[:n].astype(bool)
             s = mask
         return copy.range_count(q, r, None if groups is None else groups.on(copy), s)
+
+    def range_components(self, radius, sel=None):
+        """:meth:`FlatIndex.range_components` on the one-device copy of the rows (components need the edges
+        between shards; a multi-GPU union is not offered); ``sel``: a boolean mask, ids or a
+        :class:`MaskSelector`."""
+        r = float(range_radius(radius, 1)[0])
+        if self.ntotal == 0:
+            return np.empty((0,), dtype=np.int64), 0, 0
+        return self._one_device_copy().range_components(r, self._copy_sel(sel))
 
     def _copy_sel(self, sel):
         """A filter of this index as one over its one-device copy (rows added after a

@@ -761,6 +761,32 @@ class VectorStore:
             groups.setdefault(find(x), []).append(x)
         return [groups[root] for root in sorted(groups)]
 
+    def duplicate_labels(self, threshold: float, allowed=None) -> np.ndarray:
+        """One label per item for :meth:`find_duplicates`' grouping (an addition at the boundary; DBSCAN
+        with ``min_samples = 1``, single linkage cut at ``threshold``): int64 of length ``ntotal``, an
+        item's label the smallest id of its group -- its own id when it has no duplicate -- and ``-1`` for
+        an item ``allowed`` leaves out.  The groups form on the device (``index.range_components``): no
+        pair list is made, so a burst of a thousand copies costs a thousand labels, not half a million
+        pairs.  Without ``allowed`` the labels are valid ``group_by`` keys for :meth:`search_grouped`
+        ("one result per burst") and :meth:`facet_counts` ("matches per burst")."""
+        if self.index is None or self.index.ntotal == 0:
+            return np.empty((0,), dtype=np.int64)
+        sel = None if allowed is None else self._allowed_mask(allowed)
+        labels, _, _ = self.index.range_components(float(threshold), sel=sel)
+        return labels
+
+    def duplicate_groups(self, threshold: float, allowed=None, min_size: int = 2) -> List[List[int]]:
+        """:meth:`find_duplicates` without the pair list: the same groups in the same format -- lists of
+        item ids, each ascending, ordered by their first id -- built from :meth:`duplicate_labels`; groups
+        of fewer than ``min_size`` items are left out (``1`` keeps the items without a duplicate)."""
+        labels = self.duplicate_labels(threshold, allowed=allowed)
+        order = np.argsort(labels, kind="stable")  # by label, ascending ids within one
+        order = order[labels[order] >= 0]
+        if order.shape[0] == 0:
+            return []
+        starts = np.flatnonzero(np.diff(labels[order], prepend=-1))
+        return [g.tolist() for g in np.split(order, starts[1:]) if g.shape[0] >= int(min_size)]
+
     def cluster_items(self, n_clusters: int, allowed=None, niter: int = 20, seed: int = 1234) -> List[Dict]:
         """The items sorted into ``n_clusters`` visual groups, one cover photo each (an addition at the
         boundary; faiss's ``Kmeans`` over the rows the index holds): exact k-means on the device
