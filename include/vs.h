@@ -919,6 +919,72 @@ int vs_components_last_stats(vs_index* index, int64_t* out, int cap);
  * HIP-event time {gather + screen + refine, scan, flatten + readback} */
 int vs_components_last_times(vs_index* index, double* out, int cap);
 
+/* ==== score selectors ==========================================================================
+ * "Beach, NOT people", "only photos that look like this one", "drop everything near these rejected shots,
+ * then cluster the rest": a filter that is itself a vector predicate.  vs_sel_create takes a host bitmap,
+ * so such a filter had to go vs_range_search -> ids -> host mask -> vs_sel_create: a pair list the size of
+ * the passing rows appended, sorted and shipped, and a max_total.  These calls build the vs_sel on the
+ * device: a passing row sets one bit, nothing grows with the number of matches, there is no max_total, and
+ * the result is an ordinary vs_sel for every call that takes one (vs_search_sel, vs_search_after,
+ * vs_search_groups, vs_search_adjusted, vs_search_fused, vs_search_diverse, vs_range_search, vs_range_count,
+ * vs_range_components, vs_kmeans).
+ *
+ * Members M: rows [0, ntotal) at the time of the call, with a base selector (may be NULL) those it allows,
+ * under vs_search_sel's rules (a stale base is VS_ERR_ARG; rows added after the base was made are no members).
+ * Predicate: vs_range_search's, bit for bit.  S the canonical fp64 score, D = (float)S: row i passes query j
+ * iff D > radius[j] (inner product) or D < radius[j] (squared L2) -- strict, on the fp32 value.  Infinite
+ * radii are legal, NaN is VS_ERR_ARG.
+ * mode VS_SELQ_ANY: the row passes at least one query; VS_SELQ_ALL: every query.  nq = 0: ANY passes
+ * nothing, ALL everything, decided on the host without a scoring kernel.
+ * negate != 0: the result is M minus the passing rows.  The result is always a subset of M.
+ * The new selector covers the rows present now (n_sel = ntotal), carries the reset generation and goes
+ * stale as vs_sel_create's does; its bitmap is zero at and past n_sel, its ids ascend.
+ *
+ * vs_sel_from_range_rows: the queries are the stored values of rows ids[0, n) (any order, repeats fine),
+ * gathered on the device; a row passes its own predicate like any other row (VS_SELF_KEEP).  An id outside
+ * [0, ntotal) is VS_ERR_ARG before anything is launched.
+ *
+ * Tiers (the same bits under each; vs_set_range_mode applies), per block of at most 256 queries:
+ * SCAN: every dtype and metric, any nq, with or without a base (with one: over its id list).
+ * SCREEN: bf16 / f16, blocks of 9..256 queries, no base: the native MFMA screen started at the radius'
+ * key, then the exact refine over the survivors.  A query whose survivor list a workgroup had to cut
+ * (drop > thr0) is re-answered by the scan; its bits are kept -- each belongs to a row that passes, and
+ * setting a bit twice changes nothing.
+ * ANY: every query sets bits in one bitmap.  ALL: each query of a block has a bitmap of its own, ANDed into
+ * the accumulator after the block; a block takes min(256, staging bytes / (8 ceil(ntotal / 64))) queries, at
+ * least 1 (vs_set_scoresel_staging_bytes, process-wide, default 64 MiB).  Temporaries are counted in
+ * vs_device_bytes_live and freed before the call returns.
+ *
+ * vs_sel_combine: out = a AND b, a OR b, a AND NOT b, or NOT a (b must be NULL).  Both operands belong to
+ * `index` and its current generation (else VS_ERR_ARG).  With different n_sel the result covers the larger
+ * and the shorter operand reads as zero past its end; VS_SEL_NOT covers a's n_sel.
+ * vs_sel_bitmap: the selector's rows as vs_sel_create's bitmap, ceil(n_sel / 8) bytes, the bits at or past
+ * n_sel zero; nbytes below that is VS_ERR_ARG.
+ *
+ * Shared lock, one leased context, the calls synchronise (the shape of vs_sel_create).
+ * Not covered: vs_multi_* (build on a one-device copy); IVF and HNSW; device-pointer entry points; weighted
+ * combinations of predicates. */
+#define VS_SELQ_ANY 0
+#define VS_SELQ_ALL 1
+int vs_sel_from_range(vs_index* index, const vs_sel* base /* may be NULL */, const float* q /* host nq x d */,
+                      int64_t nq, const float* radius /* host nq */, int32_t mode, int32_t negate, vs_sel** out);
+int vs_sel_from_range_rows(vs_index* index, const vs_sel* base /* may be NULL */, const int64_t* ids, int64_t n,
+                           const float* radius /* host n */, int32_t mode, int32_t negate, vs_sel** out);
+#define VS_SEL_AND 0
+#define VS_SEL_OR 1
+#define VS_SEL_ANDNOT 2
+#define VS_SEL_NOT 3
+int vs_sel_combine(vs_index* index, const vs_sel* a, const vs_sel* b /* NULL for VS_SEL_NOT */, int32_t op,
+                   vs_sel** out);
+int vs_sel_bitmap(const vs_sel* sel, uint8_t* out /* host */, int64_t nbytes);
+int vs_set_scoresel_staging_bytes(int64_t bytes); /* >= 1 */
+/* last vs_sel_from_range / _rows on the handle, up to cap (5): {allowed rows m, members, tier taken (0: nothing
+ * was scored, VS_RANGE_SCAN, VS_RANGE_SCREEN), queries re-answered by the scan, query blocks} */
+int vs_scoresel_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/scoresel_timing.py): the last call on the handle, up to cap (3): ms of
+ * HIP-event time {screen + refine, scan (+ fold), finish (mask, count, compact)} */
+int vs_scoresel_last_times(vs_index* index, double* out, int cap);
+
 /* ==== multi-device flat index (one process, several GPUs; SURVEY.md §8 b/e) =================
  * The reference holds ONE index in ONE process (main.py:59-68 -> utils/vector_store.py:72-81); this
  * handle keeps that contract over G devices.  Rows are dealt in chunks of 2^16 consecutive ids

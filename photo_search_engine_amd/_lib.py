@@ -25,6 +25,13 @@ DTYPE_CODES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "float32": DTYPE_F32,
                "bf16": DTYPE_BF16, "bfloat16": DTYPE_BF16,
                "f16": DTYPE_F16, "fp16": DTYPE_F16, "float16": DTYPE_F16}
 
+SELQ_ANY = 0
+SELQ_ALL = 1
+SEL_AND = 0
+SEL_OR = 1
+SEL_ANDNOT = 2
+SEL_NOT = 3
+
 VS_OK = 0
 VS_ERR_ARG = -1
 VS_ERR_DEVICE = -2
@@ -176,6 +183,15 @@ _SIGS = {
     "vs_range_components": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _vp, _vp, _vp]),
     "vs_components_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_components_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    # score selectors
+    "vs_sel_from_range": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    "vs_sel_from_range_rows": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _vp, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.POINTER(_vp)]),
+    "vs_sel_combine": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_vp)]),
+    "vs_sel_bitmap": (ctypes.c_int, [_vp, _vp, _c_i64]),
+    "vs_set_scoresel_staging_bytes": (ctypes.c_int, [_c_i64]),
+    "vs_scoresel_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_scoresel_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # multi-device flat index
     "vs_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp,
                                        ctypes.POINTER(_vp)]),

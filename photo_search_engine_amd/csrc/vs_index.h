@@ -1,8 +1,8 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
 // vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip,
-// vs_fuse_host.hip, vs_after_host.hip, vs_facet_host.hip, vs_components_host.hip; the five before the last two
-// share the list-deepening driver of vs_walk.h).
+// vs_fuse_host.hip, vs_after_host.hip, vs_facet_host.hip, vs_components_host.hip, vs_scoresel_host.hip; the
+// five before the last three share the list-deepening driver of vs_walk.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -193,6 +193,12 @@ struct vs_index {
     std::mutex facet_mu;
     int64_t facet_stats[5] = {0, 0, 0, 0, 0};
     double facet_times[3] = {0, 0, 0};
+    // score selectors: the last vs_sel_from_range / _rows call's {allowed rows, members, tier taken, queries
+    // re-answered by the scan, query blocks} (vs_scoresel_last_stats) and its ms {screen + refine, scan,
+    // finish} (vs_scoresel_last_times)
+    std::mutex ss_mu;
+    int64_t ss_stats[5] = {0, 0, 0, 0, 0};
+    double ss_times[3] = {0, 0, 0};
     // duplicate groups: the last call's {members, edges, components, tier taken, queries re-answered by the
     // scan, query blocks} (vs_components_last_stats) and its ms {gather + screen + refine, scan, flatten +
     // readback} (vs_components_last_times)

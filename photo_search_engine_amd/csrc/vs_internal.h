@@ -568,6 +568,33 @@ hipError_t launch_facet_scan(const RangeArgs& a, const FacetArgs& f, bool lds, i
 hipError_t launch_facet_refine(const RangeArgs& a, const FacetArgs& f, const u64* glist, const int* gcnt, int lcap,
                                int ny, hipStream_t st);
 
+// ---- score selectors (vs_scoresel.hip) ------------------------------------------------
+// The range scan and the range refine with a bitmap in place of the pair buffer (vs_range_scan.h): a row
+// that passes radius[q] sets bit (row & 63) of word bits[q * stride_words + (row >> 6)].  stride_words 0:
+// the block's queries share one bitmap of ceil(n_valid / 64) words; otherwise each has its own, stride_words
+// (>= that many) apart.  Bits are only ever set: the host zeroes what it wants zero.
+struct BitsArgs {
+    unsigned long long* bits;
+    int64_t stride_words;
+};
+// as launch_range_scan / launch_range_refine; of RangeArgs only corpus, d, dpad, dt, metric, n_valid, q,
+// nq, radius and go are read (self_mode must be VS_SELF_KEEP, row0 0)
+hipError_t launch_bits_scan(const RangeArgs& a, const BitsArgs& b, int G, int qy, const uint32_t* ids, int64_t m,
+                            hipStream_t st);
+hipError_t launch_bits_refine(const RangeArgs& a, const BitsArgs& b, const u64* glist, const int* gcnt, int lcap, int ny,
+                              hipStream_t st);
+// acc[w] &= qbits[q * nwords + w] for every q < nqb, w < nwords
+hipError_t launch_bits_fold(uint64_t* acc, const uint64_t* qbits, int nqb, int64_t nwords, hipStream_t st);
+// out[w] = (negate ? ~acc[w] : acc[w]) & members[w] over the ceil(n_sel / 64) words of a bitmap over rows
+// [0, n_sel), the bits at or past n_sel zero; members: a bitmap over rows [0, n_members), n_members <= n_sel,
+// read as zero past its end (has_members false: every row); *total += the bits set in out
+hipError_t launch_bits_finish(const uint64_t* acc, bool has_members, const uint64_t* members, int64_t n_members,
+                              int negate, int64_t n_sel, uint64_t* out, unsigned long long* total, hipStream_t st);
+// out = a op b (VS_SEL_AND / _OR / _ANDNOT; VS_SEL_NOT: ~a, b unused) over rows [0, n_sel); a covers rows
+// [0, na), b rows [0, nb), each read as zero past its end; tail and *total as launch_bits_finish
+hipError_t launch_bits_op(const uint64_t* a, int64_t na, const uint64_t* b, int64_t nb, int op, int64_t n_sel,
+                          uint64_t* out, unsigned long long* total, hipStream_t st);
+
 // ---- duplicate groups (vs_components.hip) ---------------------------------------------
 // The range scan and the range refine with a union-find in place of the pair buffer (vs_range_scan.h):
 // every passing row of query q -- a stored row, self[q], under VS_SELF_ABOVE -- is an edge: cnt[q] += 1

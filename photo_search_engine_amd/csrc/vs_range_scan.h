@@ -1,7 +1,8 @@
 // vs_range_scan.h -- the range scan and the range refine kernels, shared by the range search
 // (vs_range.hip: passing rows appended to a pair buffer), the facet counts (vs_facet.hip: passing rows
-// counted into a per-group histogram) and the duplicate groups (vs_components.hip: passing rows united with
-// the query's own row in a union-find).  One K loop, one exact_score_rows call and one predicate; what
+// counted into a per-group histogram), the duplicate groups (vs_components.hip: passing rows united with
+// the query's own row in a union-find) and the score selectors (vs_scoresel.hip: passing rows set a bit of
+// a bitmap).  One K loop, one exact_score_rows call and one predicate; what
 // happens to a row that passes is the business of the SINK, a template parameter built from its own
 // kernel argument (SINK::Args) and the workgroup's dynamic LDS:
 //   begin(a, q)      every thread, per query: the query's state (the pair sink's region)
@@ -218,6 +219,55 @@ struct RsUnionSink {
 #pragma unroll
         for (int i = 0; i < R; ++i)
             if ((pass >> i) & 1u) cc_unite(parent, (uint32_t)self, (uint32_t)rr[i]);
+    }
+    __device__ __forceinline__ void close(int, int) const {}
+};
+
+// the score selectors' sink (vs_scoresel.hip): a passing row sets its bit in the query's bitmap,
+// bits + q * stride_words -- stride 0 (ANY): the block's queries share one bitmap; stride = the bitmap's
+// words (ALL): one bitmap per query of the block.  The rows of a wave-step are FS_NW apart, so several
+// usually fall into one 64-bit word: their bits are merged, and per distinct word of a shared bitmap one
+// relaxed agent-scope load decides whether an atomicOr is still needed (with many queries most are not).
+// Bits only ever get set, so a stale load costs an atomic and never a bit, and setting a bit twice changes
+// nothing: a query re-answered by the scan after its refine needs no clearing.  Ids index bits[0, ceil(n_valid / 64)) only: put() bounds them again.
+struct RsBitSink {
+    struct Args {
+        unsigned long long* bits;
+        int64_t stride_words;
+    };
+    unsigned long long* bits;
+    int64_t stride;
+    __device__ __forceinline__ RsBitSink(const Args& sa, uint8_t*) : bits(sa.bits), stride(sa.stride_words) {}
+    struct Q {};
+    __device__ __forceinline__ Q begin(const RangeArgs&, int) const { return {}; }
+    __device__ __forceinline__ void open(int) const {}
+    template <int METRIC, int R, bool SELF>
+    __device__ __forceinline__ void put(const RangeArgs& a, int q, float rq, const Q&, int64_t, const int64_t (&rr)[R],
+                                        const double (&s)[R]) const {
+        static_assert(!SELF, "score selectors keep the query's own row: no self id is read");
+        unsigned pass = 0u;
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (rr[i] >= 0 && rr[i] < a.n_valid && rs_pass(s[i], rq, METRIC)) pass |= 1u << i;
+        if (!pass) return;
+        unsigned long long* row = bits + (int64_t)q * stride;
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if ((pass >> i) & 1u) {
+                const int64_t w = rr[i] >> 6;
+                unsigned long long mask = 1ull << (rr[i] & 63);
+#pragma unroll
+                for (int j = i + 1; j < R; ++j)
+                    if (((pass >> j) & 1u) && (rr[j] >> 6) == w) {
+                        mask |= 1ull << (rr[j] & 63);
+                        pass &= ~(1u << j);
+                    }
+                // (a bitmap of the query's own: each of its bits is written once per tier, the load would find
+                // nothing and only put a round trip in front of the atomic -- DESIGN §7o has the A/B)
+                if (stride != 0 ||
+                    (~__hip_atomic_load(row + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & mask) != 0ull)
+                    atomicOr(row + w, mask);
+            }
     }
     __device__ __forceinline__ void close(int, int) const {}
 };

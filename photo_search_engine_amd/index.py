@@ -69,6 +69,14 @@ def range_radius(radius, nq: int) -> np.ndarray:
 
 
 SELF_MODES = {"keep": 0, "drop": 1, "above": 2}
+SELQ_MODES = {"any": _lib.SELQ_ANY, "all": _lib.SELQ_ALL}
+
+
+def selq_mode(mode) -> int:
+    """The code of a score selector's mode (``"any"`` / ``"all"``); anything else raises ``ValueError``."""
+    if mode not in SELQ_MODES:
+        raise ValueError(f"unknown score selector mode {mode!r} (\"any\" or \"all\")")
+    return SELQ_MODES[mode]
 
 
 def row_ids(ids, ntotal: int) -> np.ndarray:
@@ -270,10 +278,65 @@ class Selector:
         self._h = h
         return self
 
+    @classmethod
+    def _from_handle(cls, index: "FlatIndex", h, n: Optional[int] = None) -> "Selector":
+        """Around a ``vs_sel`` the library built on the device (:meth:`FlatIndex.selector_from_range`,
+        the set operators): there is no host bitmap until :attr:`bitmap` reads it back."""
+        self = cls.__new__(cls)
+        self._h = h
+        self._index = index
+        self._L = index._L
+        # (ntotal read after the call: rows added meanwhile are past the selector's end and read as not selected)
+        self._bitmap, self._n = None, index.ntotal if n is None else int(n)
+        return self
+
     @property
     def count(self) -> int:
         """Allowed rows."""
         return int(self._L.vs_sel_count(self._h))
+
+    @property
+    def bitmap(self) -> np.ndarray:
+        """The packed bitmap (``pack_allowed``'s layout, ``ceil(n / 8)`` bytes over the ``n`` rows the
+        selector covers, tail bits zero).  A selector built on the device reads it back once
+        (``vs_sel_bitmap``)."""
+        if self._bitmap is None:
+            if self._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+            out = np.zeros(((self._n + 7) // 8,), dtype=np.uint8)
+            check(self._L.vs_sel_bitmap(self._h, _ptr(out) if out.shape[0] else None, out.shape[0]))
+            self._bitmap = out
+        return self._bitmap
+
+    def to_mask(self) -> np.ndarray:
+        """The selector as a boolean mask over the rows it covers."""
+        return np.unpackbits(self.bitmap, bitorder="little")[: self._n].astype(bool)
+
+    def _combine(self, other, op: int) -> "Selector":
+        if other is not None and not isinstance(other, Selector):
+            return NotImplemented
+        if self._h is None or (other is not None and other._h is None):
+            raise _lib.VsError(_lib.VS_ERR_ARG, "selector is closed")
+        h = ctypes.c_void_p()
+        check(self._L.vs_sel_combine(self._index._h, self._h, None if other is None else other._h, op,
+                                     ctypes.byref(h)))
+        return Selector._from_handle(self._index, h, self._n if other is None else max(self._n, other._n))
+
+    def __and__(self, other) -> "Selector":
+        """Rows both selectors allow (``vs_sel_combine``; the operands belong to one index)."""
+        return self._combine(other, _lib.SEL_AND)
+
+    def __or__(self, other) -> "Selector":
+        """Rows either selector allows."""
+        return self._combine(other, _lib.SEL_OR)
+
+    def __sub__(self, other) -> "Selector":
+        """Rows this selector allows and ``other`` does not."""
+        return self._combine(other, _lib.SEL_ANDNOT)
+
+    def __invert__(self) -> "Selector":
+        """The rows this selector covers and does not allow."""
+        return self._combine(None, _lib.SEL_NOT)
 
     def close(self) -> None:
         if self._h is not None and self._h.value:
@@ -654,7 +717,7 @@ class FlatIndex:
         """Ascending ids of the members of a k-means call under selector ``s`` (``None``: every row)."""
         if s is None:
             return np.arange(self.ntotal, dtype=np.int64)
-        return np.flatnonzero(np.unpackbits(s._bitmap, bitorder="little")[: s._n]).astype(np.int64)
+        return np.flatnonzero(np.unpackbits(s.bitmap, bitorder="little")[: s._n]).astype(np.int64)
 
     def kmeans(self, k: int, niter: int = 20, init=None, seed: int = 1234, sel=None, metric=None) -> KMeansResult:
         """Exact k-means over the stored rows (``vs_kmeans``, include/vs.h): the members -- every row,
@@ -1072,6 +1135,55 @@ class FlatIndex:
         """A reusable :class:`Selector` over the rows present now (mask or ids, ``pack_allowed``)."""
         return Selector(self, allowed)
 
+    def selector_from_range(self, q, radius, mode: str = "any", negate: bool = False, sel=None) -> Selector:
+        """A :class:`Selector` built on the device from a score predicate (``vs_sel_from_range``,
+        include/vs.h): the rows that pass ``radius`` -- :meth:`range_search`'s predicate, a scalar or one
+        value per query -- for at least one query (``mode="any"``) or for every query (``"all"``); with
+        ``negate`` the members that do not.  Members: every row present now, under ``sel`` (as in
+        :meth:`search`) those it allows; the result is always a subset of them.  No row list is produced,
+        sorted or shipped and there is no ``max_total``.  The result is an ordinary selector: pass it as
+        ``sel=`` anywhere, combine it with ``&``, ``|``, ``-`` and ``~``."""
+        q = self._queries(q, "selector_from_range")
+        nq = q.shape[0]
+        r = range_radius(radius, nq)
+        code = selq_mode(mode)
+        h = ctypes.c_void_p()
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_sel_from_range(self._h, sh, _ptr(q) if nq else None, nq, _ptr(r) if nq else None, code,
+                                            int(bool(negate)), ctypes.byref(h)))
+        return Selector._from_handle(self, h)
+
+    def selector_from_range_rows(self, ids, radius, mode: str = "any", negate: bool = False, sel=None) -> Selector:
+        """:meth:`selector_from_range` with stored rows as the queries (``vs_sel_from_range_rows``): query
+        ``i`` is the stored value of row ``ids[i]``, gathered on the device.  A row passes its own
+        predicate like any other row, so "everything near these rows" holds the rows themselves and, with
+        ``negate``, "everything but what is near them" does not."""
+        ids = row_ids(ids, 0)  # (the library bounds them; no check here touches the handle)
+        n = ids.shape[0]
+        r = range_radius(radius, n)
+        code = selq_mode(mode)
+        h = ctypes.c_void_p()
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_sel_from_range_rows(self._h, sh, _ptr(ids) if n else None, n, _ptr(r) if n else None, code,
+                                                 int(bool(negate)), ctypes.byref(h)))
+        return Selector._from_handle(self, h)
+
+    def scoresel_last_stats(self) -> dict:
+        """The last :meth:`selector_from_range` / ``_rows``: allowed rows, members, the tier taken, the
+        queries the scan re-answered after a screen overflow and the query blocks
+        (``vs_scoresel_last_stats``)."""
+        buf = (ctypes.c_int64 * 5)()
+        check(self._L.vs_scoresel_last_stats(self._h, buf, 5))
+        return {"m": int(buf[0]), "members": int(buf[1]), "tier": {1: "scan", 2: "screen"}.get(int(buf[2]), "none"),
+                "rescanned": int(buf[3]), "blocks": int(buf[4])}
+
+    def scoresel_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`selector_from_range` / ``_rows``: screen + refine,
+        scan (and the ALL fold), finish (``vs_scoresel_last_times``)."""
+        buf = (ctypes.c_double * 3)()
+        check(self._L.vs_scoresel_last_times(self._h, buf, 3))
+        return {"screen_ms": float(buf[0]), "scan_ms": float(buf[1]), "finish_ms": float(buf[2])}
+
     def set_sel_mode(self, mode: str) -> None:
         """Force the tier of filtered searches (``"scan"``, ``"overfetch"``) or let the library choose
         (``"auto"``); results are the same bits under every mode (include/vs.h ``vs_set_sel_mode``)."""
@@ -1306,6 +1418,10 @@ class MaskSelector:
     def count(self) -> int:
         return int(np.unpackbits(self.bitmap, bitorder="little")[: self.n].sum())
 
+    def to_mask(self) -> np.ndarray:
+        """The selector as a boolean mask over the rows it covers."""
+        return np.unpackbits(self.bitmap, bitorder="little")[: self.n].astype(bool)
+
     def close(self) -> None:
         pass
 
@@ -1393,6 +1509,19 @@ def set_facet_staging_bytes(nbytes: int = FACET_STAGING_DEFAULT) -> None:
     if nbytes < 1:
         raise ValueError("facet staging bytes must be >= 1")
     check(_lib.load().vs_set_facet_staging_bytes(nbytes))
+
+
+SCORESEL_STAGING_DEFAULT = 64 << 20
+
+
+def set_scoresel_staging_bytes(nbytes: int = SCORESEL_STAGING_DEFAULT) -> None:
+    """Bound, process-wide, of the per-query bitmaps one query block of an ``"all"``
+    :meth:`FlatIndex.selector_from_range` keeps on the device (``vs_set_scoresel_staging_bytes``; below one
+    query's bitmap it acts as that bitmap).  The same bits under every value."""
+    nbytes = int(nbytes)
+    if nbytes < 1:
+        raise ValueError("score selector staging bytes must be >= 1")
+    check(_lib.load().vs_set_scoresel_staging_bytes(nbytes))
 
 
 def set_kmeans_staging_bytes(nbytes: int = KMEANS_STAGING_DEFAULT) -> None:
@@ -1678,6 +1807,36 @@ class MultiDeviceFlatIndex:
         if self.ntotal == 0:
             return np.empty((0,), dtype=np.int64), 0, 0
         return self._one_device_copy().range_components(r, self._copy_sel(sel))
+
+    def _selector_on_copy(self, build, sel) -> MaskSelector:
+        if self.ntotal == 0:
+            return MaskSelector(0, np.zeros((0,), dtype=bool))
+        copy = self._one_device_copy()
+        s = build(copy, self._copy_sel(sel))
+        try:
+            return MaskSelector(s._n, s.to_mask())
+        finally:
+            s.close()
+
+    def selector_from_range(self, q, radius, mode: str = "any", negate: bool = False, sel=None) -> MaskSelector:
+        """:meth:`FlatIndex.selector_from_range` on the one-device copy of the rows (as :meth:`range_count`);
+        ``sel``: a boolean mask, ids or a :class:`MaskSelector`.  The bitmap is read back: the result is a
+        :class:`MaskSelector` for this index's own calls."""
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"selector_from_range expects an (nq, {self.d}) array, got {q.shape}")
+        r = range_radius(radius, q.shape[0])
+        selq_mode(mode)
+        return self._selector_on_copy(lambda c, s: c.selector_from_range(q, r, mode, negate, s), sel)
+
+    def selector_from_range_rows(self, ids, radius, mode: str = "any", negate: bool = False, sel=None) -> MaskSelector:
+        """:meth:`FlatIndex.selector_from_range_rows` on the one-device copy of the rows."""
+        ids = row_ids(ids, 0)
+        r = range_radius(radius, ids.shape[0])
+        selq_mode(mode)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal):
+            raise _lib.VsError(_lib.VS_ERR_ARG, f"row ids must lie in [0, ntotal = {self.ntotal})")
+        return self._selector_on_copy(lambda c, s: c.selector_from_range_rows(ids, r, mode, negate, s), sel)
 
     def _copy_sel(self, sel):
         """A filter of this index as one over its one-device copy (rows added after a

@@ -684,6 +684,41 @@ class VectorStore:
         return {"total": int(totals[0]), "counts": {cols[g]: int(row[g]) for g in range(len(cols)) if row[g] > 0},
                 "ungrouped": int(row[len(cols)])}
 
+    def similar_to(self, query_embedding: List[float], threshold: float, allowed=None, negate: bool = False):
+        """The items :meth:`search_range` would return for ``radius = threshold`` as a selector, built on
+        the device without producing one of them (an addition at the boundary): pass it as ``allowed=`` to
+        any method -- "beach, not people" is
+        ``store.search(q_beach, 20, allowed=store.similar_to(q_people, 0.25, negate=True))``.
+        ``negate`` selects the items that do *not* match instead.  ``allowed`` restricts the items on both
+        sides: the result is always a subset of it.  The guards, the normalisation and the threshold
+        convention are :meth:`search_range`'s / :meth:`count_matches`': cosine / inner product above the
+        threshold, L2 below it, strictly.  An empty store raises ``RuntimeError`` (there is nothing to
+        select from).  Selectors combine with ``&``, ``|``, ``-`` and ``~`` on a one-GPU store."""
+        if self.index is None or self.index.ntotal == 0:
+            raise RuntimeError("the store holds no items to select from")
+        if len(query_embedding) != self.dimension:
+            raise ValueError(f"向量维度不匹配: {len(query_embedding)} != {self.dimension}")
+        sel = None if allowed is None else self._allowed_rows(allowed)
+        return self.index.selector_from_range(self._normalize_query(query_embedding), float(threshold), mode="any",
+                                              negate=bool(negate), sel=sel)
+
+    def similar_to_items(self, photo_paths, threshold: float, allowed=None, negate: bool = False, mode: str = "any"):
+        """:meth:`similar_to` with photos the store holds as the queries, their stored rows gathered on the
+        device: the items within ``threshold`` of at least one of ``photo_paths`` (``mode="all"``: of every
+        one).  A photo matches itself like any other item, so "drop everything near these rejected shots"
+        (``negate=True``) drops the shots too.  A path the store does not hold raises ``ValueError``."""
+        if self.index is None or self.index.ntotal == 0:
+            raise RuntimeError("the store holds no items to select from")
+        ids = []
+        for path in ([photo_paths] if isinstance(photo_paths, str) else list(photo_paths)):
+            index = self._path_to_index.get(path)
+            if index is None or index >= self.index.ntotal:
+                raise ValueError(f"未找到图片: {path}")
+            ids.append(index)
+        sel = None if allowed is None else self._allowed_rows(allowed)
+        return self.index.selector_from_range_rows(np.asarray(ids, dtype=np.int64), float(threshold), mode=mode,
+                                                   negate=bool(negate), sel=sel)
+
     def search_similar(self, photo_path: str, top_k: int, allowed=None) -> List[Dict]:
         """The ``top_k`` items most similar to a photo the store holds, the photo itself left out (an
         addition at the boundary): :meth:`search`'s result dicts for the stored row of ``photo_path``
@@ -713,7 +748,11 @@ class VectorStore:
     def _allowed_mask(self, allowed) -> np.ndarray:
         """``allowed`` (a boolean mask, item ids or a predicate over the metadata) as a boolean mask."""
         n = int(self.index.ntotal)
-        return np.unpackbits(pack_allowed(n, self._allowed_rows(allowed)), bitorder="little")[:n].astype(bool)
+        rows = self._allowed_rows(allowed)
+        if hasattr(rows, "to_mask"):  # a selector (similar_to): its rows, none behind them
+            got = np.asarray(rows.to_mask(), dtype=bool)[:n]
+            return np.concatenate([got, np.zeros((n - got.shape[0],), dtype=bool)])
+        return np.unpackbits(pack_allowed(n, rows), bitorder="little")[:n].astype(bool)
 
     def duplicate_pairs(self, threshold: float, allowed=None, max_pairs: Optional[int] = None):
         """Every pair of items closer than ``threshold`` -- ``distance`` above it (cosine) or below it
