@@ -907,8 +907,8 @@ int vs_facet_last_times(vs_index* index, double* out, int cap);
  * Device memory: the parent array (4 bytes per row), the per-block edge counters (2 KiB per block) and the
  * device labels (8 bytes per row), counted in vs_device_bytes_live and freed before the call returns.
  *
- * Not covered: vs_multi_* across shards (components need the edges between shards); neighbour counts per
- * row; core-point DBSCAN (min_samples > 1); a screen for f32 stores. */
+ * Not covered: vs_multi_* across shards (components need the edges between shards); a screen for f32
+ * stores.  Neighbour counts per row and core-point DBSCAN (min_samples > 1): "density clusters" below. */
 int vs_range_components(vs_index* index, const vs_sel* sel /* may be NULL */, float radius,
                         int64_t* labels /* host ntotal */, int64_t* n_components /* may be NULL */,
                         int64_t* n_edges /* may be NULL */);
@@ -918,6 +918,64 @@ int vs_components_last_stats(vs_index* index, int64_t* out, int cap);
 /* measurement hook (scripts/components_timing.py): the last call on the handle, up to cap (3): ms of
  * HIP-event time {gather + screen + refine, scan, flatten + readback} */
 int vs_components_last_times(vs_index* index, double* out, int cap);
+
+/* ==== density clusters =========================================================================
+ * Events, faces, scenes: clusters that a stray in-between frame must not fuse.  vs_range_components is
+ * single linkage and chains; DBSCAN's core points stop that: a row founds or extends a cluster only if it
+ * has at least min_samples rows within the radius, itself included (sklearn.cluster.DBSCAN's convention;
+ * Immich's minFaces).  faiss has neither this nor the per-row neighbour count under it.
+ *
+ * Members, selector and the neighbour relation are vs_range_components': members a < b are neighbours iff
+ * vs_range_search_rows(ids = {a}, radius, VS_SELF_ABOVE) under the same selector returns b -- D = (float)S
+ * passes the one scalar radius strictly.  A stale selector is VS_ERR_ARG, rows added after the selector are
+ * no members, a non-member carries no edge.
+ *   degrees[i]  the number of other members that are neighbours of i; -1 for a non-member.  The degrees of
+ *               the members sum to 2 * *n_edges.
+ *   core        a member with degrees[i] + 1 >= min_samples.  min_samples < 1 is VS_ERR_ARG.
+ *   clusters    the connected components of the neighbour relation restricted to the core rows; a cluster's
+ *               label is the smallest id of its core rows.
+ *   border      a member that is not core and has at least one core neighbour.  It takes the label of its
+ *               best core neighbour under vs_search's total order: the greatest D (inner product) or the
+ *               smallest (squared L2), D compared as floats (-0.0f and +0.0f tie), ties to the lower core
+ *               id.  The choice does not depend on the tier, the grid or the order in which edges are met (it
+ *               differs on purpose from sklearn's scan-order rule).  A border row joins one cluster only and
+ *               joins no two clusters together.
+ *   noise       a member that is neither: label -1.
+ *   labels[i]   the cluster's label, -1 for noise and for a non-member.
+ *   kinds[i]    VS_DBSCAN_NONE for a non-member, else VS_DBSCAN_NOISE / _BORDER / _CORE.
+ *   counts      {clusters, core rows, border rows, noise rows}.
+ * Identities (tests/test_gpu_dbscan.py): min_samples = 1 gives vs_range_components' labels with every member
+ * core; min_samples = 2 gives its components of two or more members, the singletons noise, no border row;
+ * degrees is the bincount of both ends of the VS_SELF_ABOVE pair list.  The labels of an unfiltered call are
+ * valid keys for vs_groups_create (noise ungrouped).
+ *
+ * A NaN radius, min_samples < 1, a null labels / degrees (the required output) with ntotal > 0 and a stale
+ * selector are VS_ERR_ARG before anything is launched.  kinds, degrees (of vs_range_dbscan), counts and
+ * n_edges may be NULL.  There is no max_total: nothing grows with the number of pairs.  Shared lock, one
+ * leased context, the call synchronises.
+ *
+ * Two passes of vs_range_components' self-join (its tiers, blocks and vs_set_range_mode): pass 1 counts the
+ * degrees and each query's edges above; pass 2 unites core rows and offers core rows to their non-core
+ * neighbours, skipping the queries -- and whole blocks -- that met no edge in pass 1.  A count is not
+ * idempotent, so under the SCREEN tier the overflow flags are read before the refine and every query is
+ * answered by exactly one of refine and scan.
+ * Device memory, freed before the call returns: 4 B (degrees) per row and 8 B per query slot; vs_range_dbscan
+ * adds 4 + 1 + 8 B per row (parent, core, best) and 8 + 1 + 8 B per row of device outputs. */
+enum { VS_DBSCAN_NONE = 0, VS_DBSCAN_NOISE = 1, VS_DBSCAN_BORDER = 2, VS_DBSCAN_CORE = 3 };
+int vs_range_degrees(vs_index* index, const vs_sel* sel /* may be NULL */, float radius,
+                     int64_t* degrees /* host ntotal */, int64_t* n_edges /* may be NULL */);
+int vs_range_dbscan(vs_index* index, const vs_sel* sel /* may be NULL */, float radius, int64_t min_samples,
+                    int64_t* labels /* host ntotal */, uint8_t* kinds /* host ntotal, may be NULL */,
+                    int64_t* degrees /* host ntotal, may be NULL */, int64_t* counts /* 4, may be NULL */,
+                    int64_t* n_edges /* may be NULL */);
+/* last vs_range_degrees / vs_range_dbscan on the handle, up to cap (12): {members, edges, clusters, core,
+ * border, noise, tier taken (VS_RANGE_SCAN / VS_RANGE_SCREEN), pass 1: queries given to the scan after a
+ * screen overflow, query blocks; pass 2: the same, query blocks run, queries skipped (no edge in pass 1)} */
+int vs_dbscan_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/dbscan_timing.py): the last call on the handle, up to cap (5): ms of HIP-event
+ * time {pass 1 gather + screen + refine, pass 1 scan, pass 2 gather + screen + refine, pass 2 scan, labels +
+ * readback} */
+int vs_dbscan_last_times(vs_index* index, double* out, int cap);
 
 /* ==== score selectors ==========================================================================
  * "Beach, NOT people", "only photos that look like this one", "drop everything near these rejected shots,

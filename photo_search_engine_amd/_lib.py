@@ -183,6 +183,10 @@ _SIGS = {
     "vs_range_components": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _vp, _vp, _vp]),
     "vs_components_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_components_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_range_degrees": (ctypes.c_int, [_vp, _vp, ctypes.c_float, _vp, _vp]),
+    "vs_range_dbscan": (ctypes.c_int, [_vp, _vp, ctypes.c_float, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "vs_dbscan_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_dbscan_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # score selectors
     "vs_sel_from_range": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     "vs_sel_from_range_rows": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, _vp, ctypes.c_int32, ctypes.c_int32,

@@ -1,7 +1,7 @@
 // vs_index.h -- the flat index object and its per-call contexts, shared by the host units of libvs
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
 // vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip,
-// vs_fuse_host.hip, vs_after_host.hip, vs_facet_host.hip, vs_components_host.hip, vs_scoresel_host.hip; the
+// vs_fuse_host.hip, vs_after_host.hip, vs_facet_host.hip, vs_components_host.hip, vs_scoresel_host.hip, vs_dbscan_host.hip; the
 // five before the last three share the list-deepening driver of vs_walk.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -205,6 +205,13 @@ struct vs_index {
     std::mutex cc_mu;
     int64_t cc_stats[6] = {0, 0, 0, 0, 0, 0};
     double cc_times[3] = {0, 0, 0};
+    // density clusters: the last vs_range_degrees / vs_range_dbscan call's {members, edges, clusters, core,
+    // border, noise, tier taken, queries pass 1 gave to the scan after a screen overflow, query blocks, the
+    // same of pass 2, query blocks pass 2 ran, pass-2 queries skipped} (vs_dbscan_last_stats) and its ms {pass 1
+    // gather + screen + refine, pass 1 scan, pass 2 the same two, labels + readback} (vs_dbscan_last_times)
+    std::mutex db_mu;
+    int64_t db_stats[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double db_times[5] = {0, 0, 0, 0, 0};
     int last_kernel_kind = 0;  // 1 = mfma, 2 = gemv, 3 = int8 mfma, 4 = int8 gemv, 5 = exact full scan
     // Screen health (first passes of MFMA batches): the certificate-failure count of a batch is read
     // back without a host wait (pinned word + event, observed by a later search).  A failed query

@@ -611,6 +611,44 @@ hipError_t launch_cc_refine(const RangeArgs& a, uint32_t* parent, const u64* gli
 hipError_t launch_cc_labels(uint32_t* parent, const uint32_t* sel_ids, int64_t m, int64_t n, int64_t* labels,
                             hipStream_t st);
 
+// ---- density clusters (vs_dbscan.hip) -------------------------------------------------
+// The self-join of the duplicate groups with one of two sinks (vs_range_scan.h).  deg set: pass 1 -- every
+// passing row of query q is an edge: cnt[q] += 1, deg[self[q]] += 1, deg[row] += 1 (deg[0, n_valid), zeroed
+// by the caller; an add is not idempotent, so no query may be answered twice).  deg null: pass 2 -- an edge
+// between two rows with core[] set joins their trees in parent[0, n_valid); an edge with one core end
+// raises best[the other end] to the core row's key; cnt is not written.
+struct DbSinkArgs {
+    uint32_t* deg;             // pass 1
+    uint32_t* parent;          // pass 2 (launch_cc_init first)
+    const uint8_t* core;       // pass 2
+    unsigned long long* best;  // pass 2 (zeroed by the caller)
+};
+// as launch_cc_scan / launch_cc_refine
+hipError_t launch_db_scan(const RangeArgs& a, const DbSinkArgs& s, int G, int qy, const uint32_t* ids, int64_t m,
+                          hipStream_t st);
+hipError_t launch_db_refine(const RangeArgs& a, const DbSinkArgs& s, const u64* glist, const int* gcnt, int lcap, int ny,
+                            hipStream_t st);
+// core[id] = deg[id] + 1 >= min_samples for the m members (as launch_cc_labels names them); the caller zeroes
+// core[0, n) first
+hipError_t launch_db_core(const uint32_t* deg, const uint32_t* sel_ids, int64_t m, int64_t n, int64_t min_samples,
+                          uint8_t* core, hipStream_t st);
+// for the m members: degrees[id] = deg[id]; with labels set also labels[id] / kinds[id] = the root of its own
+// tree / VS_DBSCAN_CORE for a core row, the root of best[id]'s core row / VS_DBSCAN_BORDER for a row with
+// best[id] != 0, -1 / VS_DBSCAN_NOISE for the rest.  The caller fills labels and degrees with -1 and kinds
+// with 0 first.
+struct DbLabelArgs {
+    const uint32_t* deg;
+    uint32_t* parent;
+    const uint8_t* core;
+    const unsigned long long* best;
+    const uint32_t* sel_ids;
+    int64_t m, n;
+    int64_t* labels;
+    uint8_t* kinds;
+    int64_t* degrees;
+};
+hipError_t launch_db_labels(const DbLabelArgs& a, hipStream_t st);
+
 // ---- queries taken from stored rows (vs_rows.hip) -----------------------------------------------
 // exact lists [nq][kk] (best first, -1 padded) -> [nq][k], k <= kk, with the entry whose id is self[q]
 // taken out and the rest moved up; a list that does not hold self[q] keeps its first k entries; slots

@@ -2,7 +2,8 @@
 // (vs_range.hip: passing rows appended to a pair buffer), the facet counts (vs_facet.hip: passing rows
 // counted into a per-group histogram), the duplicate groups (vs_components.hip: passing rows united with
 // the query's own row in a union-find) and the score selectors (vs_scoresel.hip: passing rows set a bit of
-// a bitmap).  One K loop, one exact_score_rows call and one predicate; what
+// a bitmap) and the density clusters (vs_dbscan.hip: passing rows counted into both ends' degrees, then
+// united or offered as a border row's core neighbour).  One K loop, one exact_score_rows call and one predicate; what
 // happens to a row that passes is the business of the SINK, a template parameter built from its own
 // kernel argument (SINK::Args) and the workgroup's dynamic LDS:
 //   begin(a, q)      every thread, per query: the query's state (the pair sink's region)
@@ -219,6 +220,100 @@ struct RsUnionSink {
 #pragma unroll
         for (int i = 0; i < R; ++i)
             if ((pass >> i) & 1u) cc_unite(parent, (uint32_t)self, (uint32_t)rr[i]);
+    }
+    __device__ __forceinline__ void close(int, int) const {}
+};
+
+// ---- density clusters (vs_dbscan.hip) --------------------------------------------------
+// Both sinks take their queries from stored rows under VS_SELF_ABOVE and apply the union sink's test; ids
+// index deg / core / best / parent [0, n_valid) only, and put() bounds both ends again.
+
+// pass 1, the neighbour counts: an edge (self, id) is one neighbour more for either end.  The wave-step's
+// passing rows go to the block's cnt[q] with one atomic (the query's "edges above", which pass 2 reads to
+// skip the queries that meet none), to deg[self] with one more, and each passing row's deg[id] gets 1.
+// An add is not idempotent: the host gives every query to exactly one tier (vs_dbscan_host.hip).
+struct RsDegreeSink {
+    struct Args {
+        uint32_t* deg;  // [n_valid], zeroed by the host
+    };
+    uint32_t* deg;
+    __device__ __forceinline__ RsDegreeSink(const Args& sa, uint8_t*) : deg(sa.deg) {}
+    struct Q {};
+    __device__ __forceinline__ Q begin(const RangeArgs&, int) const { return {}; }
+    __device__ __forceinline__ void open(int) const {}
+    template <int METRIC, int R, bool SELF>
+    __device__ __forceinline__ void put(const RangeArgs& a, int q, float rq, const Q&, int64_t self,
+                                        const int64_t (&rr)[R], const double (&s)[R]) const {
+        static_assert(SELF, "neighbour counts take their queries from stored rows");
+        if (self < 0 || self >= a.n_valid) return;
+        unsigned pass = 0u;
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (rr[i] >= 0 && rr[i] < a.n_valid && rs_self_ok(rr[i], self, a.self_mode) && rs_pass(s[i], rq, METRIC))
+                pass |= 1u << i;
+        if (!pass) return;
+        const unsigned c = (unsigned)__popc(pass);
+        atomicAdd(a.cnt + q, (unsigned long long)c);
+        atomicAdd(deg + self, c);
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if ((pass >> i) & 1u) atomicAdd(deg + rr[i], 1u);
+    }
+    __device__ __forceinline__ void close(int, int) const {}
+};
+
+// a border row's choice among its core neighbours as one 64-bit maximum: an order-preserving image of D
+// (inverted for L2, so that greater is better under either metric) above the complement of the core row's id
+// (so that of equal D the lower id wins).  -0.0f is folded into +0.0f first: the order is float equality's.
+// A passing D is no NaN, so no key is 0: 0 in best[] means "no core neighbour".
+template <int METRIC>
+__device__ __forceinline__ unsigned long long db_key(double S, uint32_t core_id) {
+    float D = (float)S;
+    if (D == 0.0f) D = 0.0f;
+    uint32_t u = __float_as_uint(D);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    if (METRIC != METRIC_IP) u = ~u;
+    return ((unsigned long long)u << 32) | (unsigned long long)(uint32_t)~core_id;
+}
+__device__ __forceinline__ uint32_t db_key_id(unsigned long long key) { return ~(uint32_t)key; }
+
+// pass 2, the clusters: an edge with both ends core joins their trees (cc_unite: a tree's root is its
+// smallest id, here its smallest core id); an edge with one end core offers that core row to the other end
+// (atomicMax on best[border]); an edge between two non-core rows does nothing.  Unions and maxima are
+// idempotent: a query answered twice changes nothing.  a.cnt is not touched: it holds pass 1's counts.
+struct RsDbscanSink {
+    struct Args {
+        uint32_t* parent;          // [n_valid], parent[i] = i before the pass
+        const uint8_t* core;       // [n_valid], 1 for a core row (k_db_core)
+        unsigned long long* best;  // [n_valid], zeroed by the host
+    };
+    uint32_t* parent;
+    const uint8_t* core;
+    unsigned long long* best;
+    __device__ __forceinline__ RsDbscanSink(const Args& sa, uint8_t*) : parent(sa.parent), core(sa.core), best(sa.best) {}
+    struct Q {};
+    __device__ __forceinline__ Q begin(const RangeArgs&, int) const { return {}; }
+    __device__ __forceinline__ void open(int) const {}
+    template <int METRIC, int R, bool SELF>
+    __device__ __forceinline__ void put(const RangeArgs& a, int, float rq, const Q&, int64_t self,
+                                        const int64_t (&rr)[R], const double (&s)[R]) const {
+        static_assert(SELF, "density clusters take their queries from stored rows");
+        if (self < 0 || self >= a.n_valid) return;
+        unsigned pass = 0u;
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if (rr[i] >= 0 && rr[i] < a.n_valid && rs_self_ok(rr[i], self, a.self_mode) && rs_pass(s[i], rq, METRIC))
+                pass |= 1u << i;
+        if (!pass) return;
+        const bool self_core = core[self] != 0;
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            if ((pass >> i) & 1u) {
+                const bool id_core = core[rr[i]] != 0;
+                if (self_core && id_core) cc_unite(parent, (uint32_t)self, (uint32_t)rr[i]);
+                else if (self_core) atomicMax(best + rr[i], db_key<METRIC>(s[i], (uint32_t)self));
+                else if (id_core) atomicMax(best + self, db_key<METRIC>(s[i], (uint32_t)rr[i]));
+            }
     }
     __device__ __forceinline__ void close(int, int) const {}
 };

@@ -68,6 +68,16 @@ def range_radius(radius, nq: int) -> np.ndarray:
     return np.ascontiguousarray(r)
 
 
+def dbscan_min_samples(min_samples) -> int:
+    """``min_samples`` of the density clusters as an int: an integer >= 1 (the row counts itself); anything
+    else raises ``ValueError``."""
+    if isinstance(min_samples, (bool, np.bool_)) or not isinstance(min_samples, (int, np.integer)):
+        raise ValueError(f"min_samples must be an integer >= 1, got {min_samples!r}")
+    if int(min_samples) < 1:
+        raise ValueError(f"min_samples must be >= 1, got {int(min_samples)}")
+    return int(min_samples)
+
+
 SELF_MODES = {"keep": 0, "drop": 1, "above": 2}
 SELQ_MODES = {"any": _lib.SELQ_ANY, "all": _lib.SELQ_ALL}
 
@@ -1131,6 +1141,61 @@ class FlatIndex:
         check(self._L.vs_components_last_times(self._h, buf, 3))
         return {"screen_ms": float(buf[0]), "scan_ms": float(buf[1]), "readback_ms": float(buf[2])}
 
+    def range_degrees(self, radius, sel=None):
+        """Exact neighbour counts (``vs_range_degrees``, include/vs.h "density clusters"): for every member --
+        every stored row, under ``sel`` the rows it allows -- the number of other members within ``radius``
+        (:meth:`range_components`' relation).  Returns ``(degrees, n_edges)``: ``degrees`` int64 ``(ntotal,)``,
+        ``-1`` for a row that is no member; the members' degrees sum to ``2 * n_edges``."""
+        r = float(range_radius(radius, 1)[0])  # (one scalar; NaN raises ValueError)
+        degrees = np.full((self.ntotal,), -1, dtype=np.int64)
+        ne = ctypes.c_int64(0)
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_range_degrees(self._h, sh, r, _ptr(degrees) if degrees.shape[0] else None,
+                                           ctypes.byref(ne)))
+        return degrees, int(ne.value)
+
+    def range_dbscan(self, radius, min_samples, sel=None):
+        """Exact density clusters (``vs_range_dbscan``, include/vs.h): DBSCAN over the members with
+        :meth:`range_components`' relation.  A member is core when it has at least ``min_samples`` members
+        within ``radius``, itself included; clusters are the components of the core rows, labelled by their
+        smallest core id; a non-core member with a core neighbour is a border row of its best core neighbour's
+        cluster (the best score, ties to the lower id); the rest is noise.  Returns ``(labels, kinds,
+        degrees, counts)``: ``labels`` int64 ``(ntotal,)``, ``-1`` for noise and non-members; ``kinds`` uint8
+        (``0`` non-member, ``1`` noise, ``2`` border, ``3`` core); ``degrees`` as :meth:`range_degrees`;
+        ``counts`` a dict of ``clusters``, ``core``, ``border``, ``noise`` and ``edges``."""
+        r = float(range_radius(radius, 1)[0])
+        ms = dbscan_min_samples(min_samples)
+        n = self.ntotal
+        labels = np.full((n,), -1, dtype=np.int64)
+        kinds = np.zeros((n,), dtype=np.uint8)
+        degrees = np.full((n,), -1, dtype=np.int64)
+        cnt = (ctypes.c_int64 * 4)()
+        ne = ctypes.c_int64(0)
+        with self._sel(sel) as (_, sh):
+            check(self._L.vs_range_dbscan(self._h, sh, r, ms, _ptr(labels) if n else None, _ptr(kinds) if n else None,
+                                          _ptr(degrees) if n else None, cnt, ctypes.byref(ne)))
+        return labels, kinds, degrees, {"clusters": int(cnt[0]), "core": int(cnt[1]), "border": int(cnt[2]),
+                                        "noise": int(cnt[3]), "edges": int(ne.value)}
+
+    def dbscan_last_stats(self) -> dict:
+        """The last :meth:`range_degrees` / :meth:`range_dbscan`: members, edges, clusters, core, border and
+        noise rows, the tier taken, per pass the queries given to the scan after a screen overflow and the
+        query blocks run, and the queries pass 2 skipped (``vs_dbscan_last_stats``)."""
+        buf = (ctypes.c_int64 * 12)()
+        check(self._L.vs_dbscan_last_stats(self._h, buf, 12))
+        return {"members": int(buf[0]), "edges": int(buf[1]), "clusters": int(buf[2]), "core": int(buf[3]),
+                "border": int(buf[4]), "noise": int(buf[5]), "tier": {1: "scan", 2: "screen"}.get(int(buf[6]), "none"),
+                "rescanned": int(buf[7]), "blocks": int(buf[8]), "rescanned2": int(buf[9]), "blocks2": int(buf[10]),
+                "skipped": int(buf[11])}
+
+    def dbscan_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`range_degrees` / :meth:`range_dbscan`: per pass gather +
+        screen + refine and scan, then labels + readback (``vs_dbscan_last_times``)."""
+        buf = (ctypes.c_double * 5)()
+        check(self._L.vs_dbscan_last_times(self._h, buf, 5))
+        return {"pass1_screen_ms": float(buf[0]), "pass1_scan_ms": float(buf[1]), "pass2_screen_ms": float(buf[2]),
+                "pass2_scan_ms": float(buf[3]), "labels_ms": float(buf[4])}
+
     def selector(self, allowed) -> Selector:
         """A reusable :class:`Selector` over the rows present now (mask or ids, ``pack_allowed``)."""
         return Selector(self, allowed)
@@ -1807,6 +1872,22 @@ class MultiDeviceFlatIndex:
         if self.ntotal == 0:
             return np.empty((0,), dtype=np.int64), 0, 0
         return self._one_device_copy().range_components(r, self._copy_sel(sel))
+
+    def range_degrees(self, radius, sel=None):
+        """:meth:`FlatIndex.range_degrees` on the one-device copy of the rows (as :meth:`range_components`)."""
+        r = float(range_radius(radius, 1)[0])
+        if self.ntotal == 0:
+            return np.empty((0,), dtype=np.int64), 0
+        return self._one_device_copy().range_degrees(r, self._copy_sel(sel))
+
+    def range_dbscan(self, radius, min_samples, sel=None):
+        """:meth:`FlatIndex.range_dbscan` on the one-device copy of the rows (as :meth:`range_components`)."""
+        r = float(range_radius(radius, 1)[0])
+        ms = dbscan_min_samples(min_samples)
+        if self.ntotal == 0:
+            return (np.empty((0,), dtype=np.int64), np.empty((0,), dtype=np.uint8), np.empty((0,), dtype=np.int64),
+                    {"clusters": 0, "core": 0, "border": 0, "noise": 0, "edges": 0})
+        return self._one_device_copy().range_dbscan(r, ms, self._copy_sel(sel))
 
     def _selector_on_copy(self, build, sel) -> MaskSelector:
         if self.ntotal == 0:

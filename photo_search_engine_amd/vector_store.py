@@ -826,6 +826,72 @@ class VectorStore:
         starts = np.flatnonzero(np.diff(labels[order], prepend=-1))
         return [g.tolist() for g in np.split(order, starts[1:]) if g.shape[0] >= int(min_size)]
 
+    @staticmethod
+    def _density_args(threshold, min_samples=1):
+        """``threshold`` as one non-NaN float, ``min_samples`` as an integer >= 1 (``ValueError`` otherwise),
+        checked before the index is touched."""
+        t = np.asarray(threshold, dtype=np.float64)
+        if t.ndim != 0:
+            raise ValueError(f"threshold must be one scalar, got shape {t.shape}")
+        if np.isnan(t):
+            raise ValueError("threshold must not be NaN")
+        if isinstance(min_samples, (bool, np.bool_)) or not isinstance(min_samples, (int, np.integer)) \
+                or int(min_samples) < 1:
+            raise ValueError(f"min_samples must be an integer >= 1, got {min_samples!r}")
+        return float(t), int(min_samples)
+
+    def neighbor_counts(self, threshold: float, allowed=None) -> np.ndarray:
+        """How many other items lie within ``threshold`` of each item (an addition at the boundary): int64 of
+        length ``ntotal``, ``-1`` for an item ``allowed`` leaves out; ``allowed`` restricts both ends, as in
+        :meth:`duplicate_pairs`, whose pairs these counts are the bincount of.  Counted on the device
+        (``index.range_degrees``): no pair list is made."""
+        t, _ = self._density_args(threshold)
+        if self.index is None or self.index.ntotal == 0:
+            return np.empty((0,), dtype=np.int64)
+        sel = None if allowed is None else self._allowed_mask(allowed)
+        return self.index.range_degrees(t, sel=sel)[0]
+
+    def _density(self, threshold, min_samples, allowed):
+        t, ms = self._density_args(threshold, min_samples)
+        if self.index is None or self.index.ntotal == 0:
+            return np.empty((0,), dtype=np.int64), np.empty((0,), dtype=np.uint8), np.empty((0,), dtype=np.int64)
+        sel = None if allowed is None else self._allowed_mask(allowed)
+        labels, kinds, degrees, _ = self.index.range_dbscan(t, ms, sel=sel)
+        return labels, kinds, degrees
+
+    def density_labels(self, threshold: float, min_samples: int = 3, allowed=None):
+        """DBSCAN over the items (an addition at the boundary; ``sklearn.cluster.DBSCAN``'s core points, run on
+        the device by ``index.range_dbscan``): an item with at least ``min_samples`` items within
+        ``threshold``, itself included, is *core*; clusters are the connected groups of core items; an item
+        that is not core but has a core item within ``threshold`` is a *border* item of the cluster of its
+        closest core item (ties to the lower id) and bridges nothing; the rest is *noise*.  Returns
+        ``(labels, kinds)``: ``labels`` int64, a cluster's label the smallest id of its core items, ``-1`` for
+        noise and for items ``allowed`` leaves out; ``kinds`` uint8, ``0`` left out, ``1`` noise, ``2``
+        border, ``3`` core.  Unlike :meth:`duplicate_labels` a stray in-between frame does not fuse two
+        events.  The labels are valid ``group_by`` keys for :meth:`search_grouped` and
+        :meth:`facet_counts`, noise ungrouped."""
+        labels, kinds, _ = self._density(threshold, min_samples, allowed)
+        return labels, kinds
+
+    def density_clusters(self, threshold: float, min_samples: int = 3, allowed=None) -> List[Dict]:
+        """:meth:`density_labels` as one dict per cluster, ordered by label: ``{"label": the smallest core id,
+        "items": [the cluster's ids, ascending], "core": [those of them that are core], "cover": id,
+        "size": n}``; ``cover`` is the core item with the most items within ``threshold`` (ties: the lower
+        id).  Noise is left out."""
+        labels, kinds, degrees = self._density(threshold, min_samples, allowed)
+        order = np.argsort(labels, kind="stable")  # by label, ascending ids within one
+        order = order[labels[order] >= 0]
+        if order.shape[0] == 0:
+            return []
+        starts = np.flatnonzero(np.diff(labels[order], prepend=-1))
+        out = []
+        for g in np.split(order, starts[1:]):
+            core = g[kinds[g] == 3]
+            cover = int(core[np.argmax(degrees[core])])  # (argmax takes the first of equals: the lower id)
+            out.append({"label": int(labels[g[0]]), "items": g.tolist(), "core": core.tolist(), "cover": cover,
+                        "size": int(g.shape[0])})
+        return out
+
     def cluster_items(self, n_clusters: int, allowed=None, niter: int = 20, seed: int = 1234) -> List[Dict]:
         """The items sorted into ``n_clusters`` visual groups, one cover photo each (an addition at the
         boundary; faiss's ``Kmeans`` over the rows the index holds): exact k-means on the device
