@@ -724,6 +724,83 @@ int vs_fuse_last_stats(vs_index* index, int64_t* out, int cap);
  * walk that reports the scan's rows */
 int vs_fuse_last_times(vs_index* index, double* out, int cap);
 
+/* ==== multi-vector search ======================================================================
+ * "The trip with mountains, a lake and a campfire": rank groups (an album, a day, a person, a video) by
+ * the sum over the sub-queries of the best score any member reaches -- MaxSim, late interaction.  Qdrant
+ * multivectors (max_sim), Milvus embedding lists, Weaviate multi-vector and Vespa tensors are this call;
+ * faiss has none.  It cannot be assembled from per-concept top-k lists: a group mediocre on every concept
+ * can be outside each list and still win the sum.
+ *
+ * Queries: q is host fp32 nq x m x d, as vs_search_fused takes it, 1 <= m <= VS_FUSE_MAX_Q.
+ * Groups: a vs_groups object under vs_search_groups' rules -- rows with the same non-negative key form a
+ * group, a row with a negative key is a group of its own (reported with its key as given), rows added
+ * after the object was made are no members, stale groups or groups of another index are VS_ERR_ARG.
+ * Members: the covered rows, restricted by sel (may be NULL) under vs_search_sel's rules.  A group with no
+ * member under the selector does not exist for the call.
+ * Per sub-query best: S_j(row) is the canonical fp64 score, as vs_search defines it.  M_j(g) is the best
+ * S_j over the members of g in the metric's direction: a selection, bit-equal to one member's score;
+ * I_sub[j] is the lowest member id that attains it.  (Every accumulator starts at +0.0, so no S is -0.0.)
+ * Group score: F(g) = ((M_0 + M_1) + ...) + M_{m-1} in fp64, left to right, no contraction.  For L2 this
+ * is a sum of smallest distances, and lower is better.
+ * Ranking: the groups by F in the metric's direction, ties to the lower group code: grouped groups in
+ * ascending key, then the ungrouped rows in row order.
+ * Outputs (host): keys_out (int64 nq x k), F (double nq x k: the ranking value, not rounded), D_sub (float
+ * nq x k x m, may be NULL) = (float)M_j, I_sub (int64 nq x k x m, may be NULL), sizes (int64 nq x k, may be
+ * NULL) = the members of the group under the selector.  Padding as vs_search_groups pads: keys_out
+ * INT64_MIN, I_sub -1, D_sub the worst value, F -inf (inner product) or +inf (L2), sizes 0.
+ * With m = 1, keys_out, (float)F and I_sub equal vs_search_groups(k, group_size = 1)'s keys, D and I
+ * whenever the groups' best scores are distinct; with every key distinct as well it is vs_search.  F is
+ * the fp64 sum of the best scores, recomputable from vs_reconstruct'ed rows.  Permuting the sub-queries
+ * permutes D_sub / I_sub and may change F only through the order of the additions.
+ *
+ * m out of range, k < 1 or k > min(3276, VS_FUSE_WALK_MAX / m), null q / keys_out / F, stale or foreign
+ * groups or selector are VS_ERR_ARG before anything is launched; nq = 0 returns at once; an empty member
+ * set gives all padding.  Shared lock, one leased context, the call synchronises (the shape of
+ * vs_search_fused).  Scratch is counted in vs_device_bytes_live and freed before the call returns.  The
+ * first call with a groups object builds its member lists (the covered rows by (group, id) and their
+ * offsets, 4 bytes per row + 8 per group); they live until vs_groups_destroy and are counted too.
+ *
+ * Tiers (the same bits under each: both end in the same walk kernel).
+ * LISTS: the exact top-L list of every sub-query among the members, then a device walk, one workgroup per
+ * query: the groups the lists touch are its candidates, each is scored member by member against all m
+ * sub-queries, and the candidates are ranked by (F, code).  L = first, then 4 L up to min(limit,
+ * members).  A group no list touches has every M_j no better than list j's last entry S_{j,L}; rounding
+ * and addition are monotone, so its F is no better than U = ((S_{0,L} + S_{1,L}) + ...).  Complete iff
+ * the lists held every member, or there are at least k candidates and the k-th best F is strictly better
+ * than U.  A query whose candidate groups hold more than walk_rows rows goes to SCAN at once (a few huge
+ * groups otherwise make one workgroup score half the corpus; deeper lists only add candidates), and so does
+ * an open query whose walk went through more than walk_rows / 4 rows (its next lists are four times as long).  Queries
+ * open at the limit go to SCAN.  Beside the lists a walk keeps 12 m + 8 bytes of scratch per list entry and
+ * query, about 64 MiB per launch (queries beyond that go in further launches).
+ * SCAN: a streaming scan over the members scores every row against all m sub-queries in one pass and keeps,
+ * per (query, sub-query, group), the maximum of an order-preserving 64-bit image of S in a device table
+ * (blocks of queries bounded by vs_set_maxsim_staging_bytes); a rank kernel forms F per group and keeps
+ * the k best; the walk then reports those groups.
+ * AUTO: LISTS, then SCAN for what stays open.  vs_set_maxsim_mode forces SCAN, or LISTS with the same
+ * fall-through. */
+int vs_search_maxsim(vs_index* index, const vs_groups* groups, const vs_sel* sel /* may be NULL */,
+                     const float* q /* host nq x m x d */, int64_t nq, int32_t m, int32_t k, int64_t* keys_out,
+                     double* F, float* D_sub, int64_t* I_sub, int64_t* sizes);
+#define VS_MAXSIM_AUTO 0
+#define VS_MAXSIM_LISTS 1
+#define VS_MAXSIM_SCAN 2
+int vs_set_maxsim_mode(vs_index* index, int tier);
+/* list lengths the walk is fed and the row cap of one walk (the same bits under every setting): first = 0
+ * -> max(4 k, 64), limit = 0 -> min(3276, VS_FUSE_WALK_MAX / m), walk_rows = 0 -> 400 min(nq, 256); 1 <=
+ * first <= limit <= 3276, and a call cuts both to its own default limit */
+int vs_set_maxsim_depth(vs_index* index, int32_t first, int32_t limit, int64_t walk_rows);
+/* bytes of the scan's table per block of queries (process-wide, default 64 MiB; below one query's table
+ * it acts as that table) */
+int vs_set_maxsim_staging_bytes(int64_t bytes); /* >= 1 */
+/* last call on the handle, up to cap (7): {queries, complete after the first list, complete after a deeper
+ * list, answered by the scan, longest list walked, tier taken (VS_MAXSIM_LISTS / VS_MAXSIM_SCAN), rows of
+ * the candidate groups the answering walks went through} */
+int vs_maxsim_last_stats(vs_index* index, int64_t* out, int cap);
+/* measurement hook (scripts/maxsim_timing.py): the last call on the handle, up to cap (7): ms of HIP-event
+ * time {list search, walk} of the first list and of the deeper lists, of the scan, of the rank and of the
+ * final walk */
+int vs_maxsim_last_times(vs_index* index, double* out, int cap);
+
 /* ==== paged search =============================================================================
  * "Load more": continue a ranking after a cursor row.  Every ranking above stops at k <= 3276; this call
  * returns the k rows that follow a given row of vs_search's ranking, exactly, at any depth, without

@@ -166,6 +166,14 @@ _SIGS = {
     "vs_set_fuse_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32]),
     "vs_fuse_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "vs_fuse_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    # multi-vector search
+    "vs_search_maxsim": (ctypes.c_int, [_vp, _vp, _vp, _vp, _c_i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp,
+                                        _vp]),
+    "vs_set_maxsim_mode": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "vs_set_maxsim_depth": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_i64]),
+    "vs_set_maxsim_staging_bytes": (ctypes.c_int, [_c_i64]),
+    "vs_maxsim_last_stats": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "vs_maxsim_last_times": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     # paged search
     "vs_search_after": (ctypes.c_int, [_vp, _vp, _vp, _c_i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "vs_set_after_mode": (ctypes.c_int, [_vp, ctypes.c_int]),

@@ -18,7 +18,7 @@ SOURCES = ["vs_kernels.hip", "vs_api.hip", "vs_store.hip", "vs_search.hip", "vs_
            "vs_adjust.hip", "vs_adjust_host.hip", "vs_fuse.hip", "vs_fuse_host.hip",
            "vs_after.hip", "vs_after_host.hip", "vs_facet.hip", "vs_facet_host.hip",
            "vs_components.hip", "vs_components_host.hip", "vs_scoresel.hip", "vs_scoresel_host.hip",
-           "vs_dbscan.hip", "vs_dbscan_host.hip"]
+           "vs_dbscan.hip", "vs_dbscan_host.hip", "vs_maxsim.hip", "vs_maxsim_host.hip"]
 ARCH = os.environ.get("VS_OFFLOAD_ARCH", "gfx950")
 
 

@@ -314,6 +314,8 @@ void vs_groups_destroy(vs_groups* gr) {
     gr->gkey.release();
     gr->gsize.release();
     gr->ukey.release();
+    gr->ml_rows.release();
+    gr->ml_off.release();
     if (prev >= 0 && prev != gr->device) (void)hipSetDevice(prev);
     delete gr;
 }

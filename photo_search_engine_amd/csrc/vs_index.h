@@ -181,6 +181,13 @@ struct vs_index {
     // (vs_fuse_last_stats) and its ms {search, walk} per list tier, scan, the scan's walk (vs_fuse_last_times)
     vs::WalkState fu;
     std::atomic<int> fuse_mode{VS_FUSE_AUTO};
+    // multi-vector search (vs_set_maxsim_depth, vs_set_maxsim_mode): the last call's {queries, complete after
+    // the first list, after a deeper list, answered by the scan, longest list walked, tier taken, candidate
+    // rows walked} (vs_maxsim_last_stats) and its ms {search, walk} per list tier, scan, rank, the scan's walk
+    // (vs_maxsim_last_times); the row cap of one walk (0 = default)
+    vs::WalkState mx;
+    std::atomic<int> maxsim_mode{VS_MAXSIM_AUTO};
+    std::atomic<int64_t> maxsim_walk_rows{0};
     // paged search (vs_set_after_depth, vs_set_after_mode): the last call's {queries, complete after the
     // first list, after a deeper list, answered by the scan, longest list walked, tier taken}
     // (vs_after_last_stats) and its ms {search, cut} per list tier, cursor scoring, scan (vs_after_last_times)
@@ -255,6 +262,12 @@ struct vs_groups {
     vs::DevBuf gkey;   // int64 [G] keys, ascending
     vs::DevBuf gsize;  // int32 [G] rows per group
     vs::DevBuf ukey;   // int64 [U] keys of the ungrouped rows, in row order
+    // the member lists, made under ml_mu by the first multi-vector call with the object (vs_maxsim_host.hip);
+    // a group's code is its index in gkey, or G + u for the u-th ungrouped row
+    mutable std::mutex ml_mu;
+    mutable bool ml_built = false;
+    mutable vs::DevBuf ml_rows;  // uint32 [n_cov] the covered rows by (code, id)
+    mutable vs::DevBuf ml_off;   // int64 [G + U + 1] where each code's rows begin
 };
 
 // ---- score adjustment: exact adjusted search (include/vs.h "adjusted search"; kernels: vs_adjust.hip) ----

@@ -834,6 +834,66 @@ hipError_t launch_fuse_walk(const FuseWalkArgs& a, int nq, hipStream_t st);
 hipError_t launch_fuse_scan(const FullScanArgs& a, int m, int mode, const uint32_t* ids, int64_t n_ids, int qy,
                             hipStream_t st);
 
+// ---- multi-vector search (vs_maxsim.hip) ---------------------------------------------
+// A group's score is F = ((M_0 + M_1) + ...) + M_{m-1}, M_j the best canonical fp64 score of a member with
+// sub-query j.  A group's code is its index among the distinct non-negative keys, or G + u for the u-th
+// ungrouped row: codes [0, ncodes), ncodes = G + U; the member lists are ml_rows [n_cov] (rows by (code,
+// id)) and ml_off [ncodes + 1].
+struct MaxsimGroups {
+    const int32_t* gid;       // [n_cov] group codes as vs_groups keeps them (ungrouped row u: ~u)
+    int64_t n_cov, G, ncodes;
+    const uint32_t* ml_rows;  // [n_cov]
+    const int64_t* ml_off;    // [ncodes + 1]
+    const int64_t* gkey;      // [G]
+    const int64_t* ukey;      // [U]
+};
+struct MaxsimWalkArgs {
+    const uint8_t* corpus;  // tiled shard
+    int d, dpad, dt, metric;
+    int64_t n_valid;
+    MaxsimGroups g;
+    const uint64_t* sel_bits;  // the members' bitmap over rows [0, n_sel), or null: every covered row
+    int64_t n_sel;
+    const float* q;         // [nq][m][d] fp32 sub-queries of the launch's queries
+    int m;
+    const int64_t* cand;    // [nq][nl][L]: row ids, best first (an entry < 0 ends a list), or group codes (codes = 1)
+    int nl;                 // m (list j is sub-query j's exact ranking) or 1 (the rank kernel's codes)
+    int64_t L;              // nl * L <= FUSE_WALK_MAX
+    int codes;              // 1: cand holds group codes; never certified, never capped
+    int hold_all;           // 1: the lists held every member: complete whatever the bound says, no row cap
+    int64_t walk_rows;      // a query whose candidate groups hold more rows stays open (lists only)
+    int k;
+    double* M_tmp;          // [nq][nl L][m] scratch: the candidate groups' best scores
+    uint32_t* I_tmp;        // [nq][nl L][m] scratch: the lowest member ids that attain them
+    uint32_t* C_tmp;        // [nq][nl L] scratch: the distinct candidate codes, ascending
+    int32_t* Z_tmp;         // [nq][nl L] scratch: members of each candidate group under the selector
+    int64_t* keys;          // [nq][k] group keys, INT64_MIN padded
+    double* F;              // [nq][k], padded with -+inf
+    float* D_sub;           // [nq][k][m] (float)M_j, padded with the worst score
+    int64_t* I_sub;         // [nq][k][m], -1 padded
+    int64_t* sizes;         // [nq][k], 0 padded
+    int32_t* complete;      // [nq] 1 complete, 0 open (deeper lists may close it), 2 over the row cap (only the scan can)
+    int64_t* walked;        // [nq] rows of the candidate groups' member lists
+};
+size_t maxsim_walk_lds(int64_t n_entries, int d, int m, bool* qlds);  // dynamic LDS of one walk workgroup
+hipError_t launch_maxsim_walk(const MaxsimWalkArgs& a, int nq, hipStream_t st);
+// the scan: table [nq][m][ncodes] (zeroed) takes the 64-bit maximum of the order-preserving image of every
+// member's S_j.  ids null = rows [0, g.n_cov), else the n_ids listed rows (ascending, each < g.n_cov); G
+// workgroups split the sequence, qy (1..nq) slices deal the queries.
+struct MaxsimScanArgs {
+    const uint8_t* corpus;
+    int d, dpad, dt, metric;
+    MaxsimGroups g;
+    const float* q;  // [nq][m][d]
+    int nq, m;
+    unsigned long long* table;
+    int variant;  // measurement only: bit 0 = lane 0 offers every pair, bit 1 = a relaxed load in front of the atomic
+};
+hipError_t launch_maxsim_scan(const MaxsimScanArgs& a, const uint32_t* ids, int64_t n_ids, int G, int qy, hipStream_t st);
+// the rank: per query the k best codes under (F, code) out of the table, as cand [nq][k] (-1 padded)
+hipError_t launch_maxsim_rank(const unsigned long long* table, int nq, int m, int64_t ncodes, int metric, int k,
+                              int64_t* cand, hipStream_t st);
+
 // ---- paged search (vs_after.hip) -----------------------------------------------------
 // A query's cursor is the position (S*, c) in vs_search's total order: c a stored row (or -1: from the
 // top), S* its canonical fp64 score with the query.  On the device S* is held as the scan's key, S or -S

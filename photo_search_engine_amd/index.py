@@ -468,6 +468,48 @@ FUSE_KINDS = {"any": 0, "all": 1}  # VS_FUSE_ANY / VS_FUSE_ALL
 FUSE_MODES = {"auto": 0, "lists": 1, "scan": 2}  # VS_FUSE_*
 FUSE_MAX_Q = 8  # VS_FUSE_MAX_Q
 AFTER_MODES = {"auto": 0, "lists": 1, "scan": 2}  # VS_AFTER_*
+MAXSIM_MODES = {"auto": 0, "lists": 1, "scan": 2}  # VS_MAXSIM_*
+MAXSIM_STAGING_DEFAULT = 64 << 20
+
+
+def maxsim_k_limit(m: int) -> int:
+    """The largest ``k`` of a multi-vector search with ``m`` sub-queries: ``min(3276, VS_FUSE_WALK_MAX // m)``."""
+    return min(GROUP_KG_MAX, 8192 // int(m))
+
+
+def maxsim_args(q, k, d: int):
+    """``(q, m, k)`` of a multi-vector search, checked before any library call: ``q`` a contiguous fp32
+    ``(nq, m, d)`` array with ``1 <= m <= FUSE_MAX_Q`` and ``1 <= k <= maxsim_k_limit(m)``, else
+    ``ValueError``."""
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    if q.ndim != 3 or q.shape[2] != int(d):
+        raise ValueError(f"search_maxsim expects an (nq, m, {int(d)}) array, got {q.shape}")
+    m, k = q.shape[1], int(k)
+    if not 1 <= m <= FUSE_MAX_Q:
+        raise ValueError(f"search_maxsim takes 1..{FUSE_MAX_Q} sub-queries per query, got {m}")
+    if k < 1:
+        raise _lib.VsError(_lib.VS_ERR_ARG, "k must be >= 1")
+    return q, m, k  # (the library rejects k above maxsim_k_limit(m))
+
+
+class MaxSimResult:
+    """What :meth:`FlatIndex.search_maxsim` returns.  ``keys`` (nq, k) int64: the groups, best first (an
+    ungrouped row's negative key as given; ``KEY_PAD`` past the last group); ``scores`` (nq, k) float64: the
+    group scores, ``-inf`` / ``+inf`` (L2) padded; ``sub_scores`` (nq, k, m) float32: the best member score
+    per sub-query, padded with the worst score; ``sub_ids`` (nq, k, m) int64: the lowest member id that
+    attains it, ``-1`` padded; ``sizes`` (nq, k) int64: the members the group has under the selector."""
+
+    __slots__ = ("keys", "scores", "sub_scores", "sub_ids", "sizes")
+
+    def __init__(self, keys, scores, sub_scores, sub_ids, sizes) -> None:
+        self.keys = keys
+        self.scores = scores
+        self.sub_scores = sub_scores
+        self.sub_ids = sub_ids
+        self.sizes = sizes
+
+    def __iter__(self):
+        return iter((self.keys, self.scores, self.sub_scores, self.sub_ids, self.sizes))
 
 
 def after_arrays(nq: int, after, rank_hint=None):
@@ -977,6 +1019,60 @@ class FlatIndex:
         check(self._L.vs_fuse_last_times(self._h, buf, 6))
         return {"search_ms": [float(buf[0]), float(buf[2])], "walk_ms": [float(buf[1]), float(buf[3])],
                 "scan_ms": float(buf[4]), "scan_walk_ms": float(buf[5])}
+
+    def search_maxsim(self, q, k: int, groups: Groups, sel=None) -> MaxSimResult:
+        """Exact top-``k`` groups by summed best matches (``vs_search_maxsim``, include/vs.h): ``q`` is
+        ``(nq, m, d)``, one query per ``m`` sub-queries (``1 <= m <= 8``).  A group's score is the fp64 sum,
+        left to right, of the best score any of its members -- the rows ``groups`` covers, under ``sel``
+        those of them it allows -- reaches under each sub-query; the groups are ranked by it in the metric's
+        direction, ties to the lower group.  ``k`` is at most ``maxsim_k_limit(m)``.  Returns a
+        :class:`MaxSimResult`."""
+        q, m, k = maxsim_args(q, k, self.d)
+        if not isinstance(groups, Groups):
+            raise TypeError("groups must be a Groups object (FlatIndex.group_keys)")
+        nq = q.shape[0]
+        keys = np.empty((nq, k), dtype=np.int64)
+        F = np.empty((nq, k), dtype=np.float64)
+        U = np.empty((nq, k, m), dtype=np.float32)
+        J = np.empty((nq, k, m), dtype=np.int64)
+        sizes = np.empty((nq, k), dtype=np.int64)
+        with self._sel(sel) as (_, sh):
+            if groups._h is None:
+                raise _lib.VsError(_lib.VS_ERR_ARG, "groups are closed")
+            check(self._L.vs_search_maxsim(self._h, groups._h, sh, _ptr(q), nq, m, k, _ptr(keys), _ptr(F), _ptr(U),
+                                           _ptr(J), _ptr(sizes)))
+        return MaxSimResult(keys, F, U, J, sizes)
+
+    def set_maxsim_mode(self, mode: str) -> None:
+        """Force the tier of multi-vector searches (``"lists"``, ``"scan"``) or let the library choose
+        (``"auto"``); the same bits under every mode (``vs_set_maxsim_mode``)."""
+        if mode not in MAXSIM_MODES:
+            raise ValueError(f"maxsim tier must be one of {sorted(MAXSIM_MODES)}")
+        check(self._L.vs_set_maxsim_mode(self._h, MAXSIM_MODES[mode]))
+
+    def set_maxsim_depth(self, first: int = 0, limit: int = 0, walk_rows: int = 0) -> None:
+        """The list lengths :meth:`search_maxsim` walks -- the first list and the longest one -- and the rows
+        one walk may go through before its query is left to the scan (``0`` = the defaults; the same bits
+        under every setting, ``vs_set_maxsim_depth``)."""
+        check(self._L.vs_set_maxsim_depth(self._h, int(first), int(limit), int(walk_rows)))
+
+    def maxsim_last_stats(self) -> dict:
+        """The last :meth:`search_maxsim`: queries, how many were complete after the first list, after a
+        deeper list, how many the scan answered, the longest list walked, the tier taken and the rows of the
+        candidate groups the answering walks went through (``vs_maxsim_last_stats``)."""
+        buf = (ctypes.c_int64 * 7)()
+        check(self._L.vs_maxsim_last_stats(self._h, buf, 7))
+        tier = {v: n for n, v in MAXSIM_MODES.items()}[int(buf[5])]
+        return {"queries": int(buf[0]), "first": int(buf[1]), "deeper": int(buf[2]), "scan": int(buf[3]),
+                "longest": int(buf[4]), "tier": tier, "walked": int(buf[6])}
+
+    def maxsim_last_times(self) -> dict:
+        """HIP-event milliseconds of the last :meth:`search_maxsim`: list search and walk per list tier, the
+        scan, the rank and the final walk (``vs_maxsim_last_times``)."""
+        buf = (ctypes.c_double * 7)()
+        check(self._L.vs_maxsim_last_times(self._h, buf, 7))
+        return {"search_ms": [float(buf[0]), float(buf[2])], "walk_ms": [float(buf[1]), float(buf[3])],
+                "scan_ms": float(buf[4]), "rank_ms": float(buf[5]), "scan_walk_ms": float(buf[6])}
 
     def search_after(self, q, k: int, after, sel=None, rank_hint=None, return_rank: bool = False):
         """The ``k`` rows that follow a cursor row in :meth:`search`'s ranking (``vs_search_after``,
@@ -1587,6 +1683,16 @@ def set_scoresel_staging_bytes(nbytes: int = SCORESEL_STAGING_DEFAULT) -> None:
     if nbytes < 1:
         raise ValueError("score selector staging bytes must be >= 1")
     check(_lib.load().vs_set_scoresel_staging_bytes(nbytes))
+
+
+def set_maxsim_staging_bytes(nbytes: int = MAXSIM_STAGING_DEFAULT) -> None:
+    """Bound, process-wide, of the per-group table one query block of :meth:`FlatIndex.search_maxsim`'s scan
+    keeps on the device (``vs_set_maxsim_staging_bytes``; below one query's table it acts as that table).
+    The same bits under every value."""
+    nbytes = int(nbytes)
+    if nbytes < 1:
+        raise ValueError("maxsim staging bytes must be >= 1")
+    check(_lib.load().vs_set_maxsim_staging_bytes(nbytes))
 
 
 def set_kmeans_staging_bytes(nbytes: int = KMEANS_STAGING_DEFAULT) -> None:

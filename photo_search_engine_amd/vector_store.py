@@ -514,6 +514,61 @@ class VectorStore:
                 for distance, index, which, sub in zip(D[0].tolist(), I[0].tolist(), W[0].tolist(), U[0].tolist())
                 if index != -1]
 
+    def search_multivector(self, query_embeddings: List[List[float]], top_k: int, group_by, allowed=None) -> List[Dict]:
+        """Groups ranked by several embeddings at once (an addition at the boundary; Qdrant multivectors
+        ``max_sim``, Milvus embedding lists, Weaviate multi-vector, Vespa tensors): "the trip with mountains,
+        a lake and a campfire" -- each concept matched by *some* item of the group.  A group's score is the
+        sum over the embeddings of the best score any of its items reaches (MaxSim, late interaction),
+        exact: a group mediocre on every concept can be outside every per-concept top-k list and still win,
+        so no merge of :meth:`search` results gives this ranking.  Returns the best ``top_k`` groups as
+        ``{"group": value, "score": float, "size": n, "matches": [{"metadata", "distance"}, ...]}`` with one
+        match per embedding, the group's best item under it (the earliest item among equals); ``size`` is
+        the number of items the group has (under ``allowed``).
+
+        ``group_by`` as in :meth:`search_grouped` (ungrouped items are groups of their own, reported with
+        ``"group": None``); each embedding is normalised as :meth:`search` normalises its one; the guards
+        and the ``k = min(top_k, ntotal)`` clamp are :meth:`search`'s; ``allowed`` as there.  An empty list
+        of embeddings raises ``ValueError``; at most 8 embeddings, and ``k`` beyond
+        ``min(3276, 8192 // len(query_embeddings))`` raises ``ValueError``.  HNSW stores answer through the
+        exact flat path, as filtered calls do."""
+        embeddings = list(query_embeddings)
+        if not embeddings:
+            raise ValueError("query_embeddings must hold at least one embedding")
+        if len(embeddings) > 8:
+            raise ValueError(f"search_multivector takes at most 8 embeddings, got {len(embeddings)}")
+        if self.index is None or self.index.ntotal == 0:
+            return []
+        for embedding in embeddings:
+            if len(embedding) != self.dimension:
+                raise ValueError(f"向量维度不匹配: {len(embedding)} != {self.dimension}")
+        if not hasattr(self.index, "search_maxsim"):
+            raise NotImplementedError("search_multivector needs a one-device flat index")
+        n = int(self.index.ntotal)
+        k, limit = min(int(top_k), n), min(3276, 8192 // len(embeddings))
+        if k < 1:
+            raise ValueError("top_k must be >= 1")
+        if k > limit:
+            raise ValueError(f"top_k = {k} exceeds {limit} at {len(embeddings)} embeddings")
+        q = np.stack([self._normalize_query(embedding)[0] for embedding in embeddings])[None, :, :]
+        groups, values, own = self._group_keys(group_by, n)
+        try:
+            sel = None if allowed is None else self._allowed_rows(allowed)
+            res = self.index.search_maxsim(q, k, groups, sel=sel)
+        finally:
+            if own:
+                groups.close()
+        out: List[Dict] = []
+        for slot in range(k):
+            size = int(res.sizes[0, slot])
+            if size == 0:
+                break
+            key = int(res.keys[0, slot])
+            matches = [{"metadata": self.metadata[index], "distance": float(distance)}
+                       for distance, index in zip(res.sub_scores[0, slot].tolist(), res.sub_ids[0, slot].tolist())]
+            out.append({"group": (key if values is None else values[key]) if key >= 0 else None,
+                        "score": float(res.scores[0, slot]), "size": size, "matches": matches})
+        return out
+
     def search_page(self, query_embedding: List[float], top_k: int, after=None, allowed=None) -> List[Dict]:
         """:meth:`search` continued (an addition at the boundary; Elasticsearch ``search_after``, Qdrant and
         Milvus ``offset``, Weaviate ``after``): the ``top_k`` items that follow ``after`` in the exact
