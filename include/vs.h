@@ -902,8 +902,8 @@ int vs_after_last_times(vs_index* index, double* out, int cap);
  * place of the pair buffer.
  * SCREEN: bf16 / f16, blocks of 9..256 queries, no selector: the native MFMA screen started at the
  * radius' key, then the exact refine over the survivors.  A query whose survivor list a workgroup had to
- * cut (drop > thr0) gets its counter row zeroed on the device and is re-answered by the scan: no query
- * is counted from a list that may be incomplete, no row is counted twice.
+ * cut (drop > thr0) is left alone by the refine and answered by the scan: no query is counted from a
+ * list that may be incomplete, no row is counted twice.
  * Histogram forms of the scan (the same integers under each; vs_set_facet_hist):
  * GLOBAL: one 64-bit device atomic per distinct bin among the rows a wave scored in one step;
  * LDS: G + 1 uint32 bins in the workgroup's LDS behind the query, flushed per query -- the non-zero bins
@@ -978,8 +978,7 @@ int vs_facet_last_times(vs_index* index, double* out, int cap);
  * block's first member (with a selector: over the tail of its id list from the block's first position).
  * SCREEN: bf16 / f16, blocks of 9..256 queries, no selector: the native MFMA screen started at the
  * radius' key, then the exact refine over the survivors.  A query whose survivor list a workgroup had to
- * cut (drop > thr0) gets its edge counter zeroed and is re-answered by the scan; the unions its refine
- * made stay, since uniting a joined pair again changes nothing.
+ * cut (drop > thr0) is left alone by the refine and answered by the scan.
  *
  * Device memory: the parent array (4 bytes per row), the per-block edge counters (2 KiB per block) and the
  * device labels (8 bytes per row), counted in vs_device_bytes_live and freed before the call returns.
@@ -1083,8 +1082,7 @@ int vs_dbscan_last_times(vs_index* index, double* out, int cap);
  * SCAN: every dtype and metric, any nq, with or without a base (with one: over its id list).
  * SCREEN: bf16 / f16, blocks of 9..256 queries, no base: the native MFMA screen started at the radius'
  * key, then the exact refine over the survivors.  A query whose survivor list a workgroup had to cut
- * (drop > thr0) is re-answered by the scan; its bits are kept -- each belongs to a row that passes, and
- * setting a bit twice changes nothing.
+ * (drop > thr0) is left alone by the refine and answered by the scan.
  * ANY: every query sets bits in one bitmap.  ALL: each query of a block has a bitmap of its own, ANDed into
  * the accumulator after the block; a block takes min(256, staging bytes / (8 ceil(ntotal / 64))) queries, at
  * least 1 (vs_set_scoresel_staging_bytes, process-wide, default 64 MiB).  Temporaries are counted in

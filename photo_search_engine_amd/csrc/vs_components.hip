@@ -51,74 +51,20 @@ hipError_t launch_cc_labels(uint32_t* parent, const uint32_t* sel_ids, int64_t m
 }
 
 // the range kernels with the union sink
-template <int DT, int METRIC, bool QLDS, bool SEL>
-constexpr auto k_cc_scan = k_range_scan<DT, METRIC, QLDS, SEL, true, RsUnionSink>;
-template <int DT, int METRIC, bool QLDS>
-constexpr auto k_cc_refine = k_range_refine<DT, METRIC, QLDS, true, RsUnionSink>;
-
 static bool cc_args_ok(const RangeArgs& a, const uint32_t* parent) {
-    return a.corpus && a.q && a.radius && a.cnt && a.self && parent && a.nq > 0 && a.d > 0 && a.n_valid > 0 &&
-           a.n_valid <= (int64_t)0xFFFFFFFFll && (a.metric == METRIC_IP || a.metric == METRIC_L2) &&
-           a.self_mode == VS_SELF_ABOVE && a.row0 >= 0 && a.row0 < a.n_valid;
-}
-
-template <int DT>
-static void launch_cc_scan_dt(const RangeArgs& a, uint32_t* parent, int G, int qy, const uint32_t* ids, int64_t m,
-                              hipStream_t st) {
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = qbytes <= RS_QLDS_MAX;
-    const size_t lds = qlds ? qbytes : 0;
-    const dim3 grid(G, qy), block(FS_THREADS);
-    const bool ip = a.metric == METRIC_IP;
-    const RsUnionSink::Args sa{parent};
-#define VS_CC_SCAN(M, Q)                                                                                      \
-    do {                                                                                                      \
-        if (ids) hipLaunchKernelGGL((k_cc_scan<DT, M, Q, true>), grid, block, lds, st, a, ids, m, sa);        \
-        else hipLaunchKernelGGL((k_cc_scan<DT, M, Q, false>), grid, block, lds, st, a, ids, m, sa);           \
-    } while (0)
-    if (ip && qlds) VS_CC_SCAN(METRIC_IP, true);
-    else if (ip) VS_CC_SCAN(METRIC_IP, false);
-    else if (qlds) VS_CC_SCAN(METRIC_L2, true);
-    else VS_CC_SCAN(METRIC_L2, false);
-#undef VS_CC_SCAN
+    return a.cnt && a.self && parent && a.n_valid <= (int64_t)0xFFFFFFFFll && a.self_mode == VS_SELF_ABOVE;
 }
 
 hipError_t launch_cc_scan(const RangeArgs& a, uint32_t* parent, int G, int qy, const uint32_t* ids, int64_t m,
                           hipStream_t st) {
-    if (!cc_args_ok(a, parent) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) ||
-        (!ids && m != 0) || (ids && a.row0 != 0))
-        return hipErrorInvalidValue;
-    if (a.dt == DT_F32) launch_cc_scan_dt<DT_F32>(a, parent, G, qy, ids, m, st);
-    else if (a.dt == DT_BF16) launch_cc_scan_dt<DT_BF16>(a, parent, G, qy, ids, m, st);
-    else if (a.dt == DT_F16) launch_cc_scan_dt<DT_F16>(a, parent, G, qy, ids, m, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-template <int DT>
-static void launch_cc_refine_dt(const RangeArgs& a, uint32_t* parent, const u64* glist, const int* gcnt, int lcap,
-                                int ny, hipStream_t st) {
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = qbytes <= RS_QLDS_MAX;
-    const size_t lds = qlds ? qbytes : 0;
-    const dim3 grid(a.nq, ny), block(FS_THREADS);
-    const bool ip = a.metric == METRIC_IP;
-    const RsUnionSink::Args sa{parent};
-#define VS_CC_REFINE(M, Q) hipLaunchKernelGGL((k_cc_refine<DT, M, Q>), grid, block, lds, st, a, glist, gcnt, lcap, sa)
-    if (ip && qlds) VS_CC_REFINE(METRIC_IP, true);
-    else if (ip) VS_CC_REFINE(METRIC_IP, false);
-    else if (qlds) VS_CC_REFINE(METRIC_L2, true);
-    else VS_CC_REFINE(METRIC_L2, false);
-#undef VS_CC_REFINE
+    if (!cc_args_ok(a, parent)) return hipErrorInvalidValue;
+    return rs_launch_scan<RsUnionSink, true>(a, {parent}, 0, 0, G, qy, ids, m, st);
 }
 
 hipError_t launch_cc_refine(const RangeArgs& a, uint32_t* parent, const u64* glist, const int* gcnt, int lcap, int ny,
                             hipStream_t st) {
-    if (!cc_args_ok(a, parent) || !glist || !gcnt || lcap <= 0 || ny < 1 || ny > 65535) return hipErrorInvalidValue;
-    if (a.dt == DT_BF16) launch_cc_refine_dt<DT_BF16>(a, parent, glist, gcnt, lcap, ny, st);
-    else if (a.dt == DT_F16) launch_cc_refine_dt<DT_F16>(a, parent, glist, gcnt, lcap, ny, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (!cc_args_ok(a, parent)) return hipErrorInvalidValue;
+    return rs_launch_refine<RsUnionSink, true>(a, {parent}, glist, gcnt, lcap, ny, st);
 }
 
 }  // namespace vs

@@ -3,22 +3,14 @@
 //
 // The members, in ascending id, are the queries of a self-join under VS_SELF_ABOVE, staged in blocks of
 // MFMA_QB as vs_range_search_rows stages them (gathered on the device from their own rows).  A block runs
-// the range search's tiers with the union sink: nothing is appended, sorted or shipped per pair; a pair
-// costs one union in parent[] and one count.  What crosses the host per block is its edge counters (and
-// the screen's overflow flags); the labels come back once, after the last block.
-#include "vs_walk.h"
+// the range search's tiers (range_tiers, vs_range_tiers.h) with the union sink: nothing is appended, sorted
+// or shipped per pair; a pair costs one union in parent[] and one count.  What crosses the host per block is
+// its edge counters (and the screen's overflow flags); the labels come back once, after the last block.
+#include "vs_range_tiers.h"
 
 using namespace vs;
 
 namespace {
-
-constexpr int kCcScanRows = 64;  // rows per workgroup of the scan, at least (the range scan's figure)
-
-// the call's small device arrays and their host mirror
-struct CcAuxH {
-    float radius[MFMA_QB];
-    int go[MFMA_QB];
-};
 
 struct CcStats {
     int64_t members = 0, edges = 0, components = 0, tier = VS_RANGE_SCAN, rescanned = 0, blocks = 0;
@@ -72,15 +64,11 @@ int vs_range_components(vs_index* ix, const vs_sel* sel, float radius, int64_t* 
         int64_t* mem = c->row_ids.as<int64_t>();
         HIP_CHECK(launch_km_members(sel ? sel->ids : nullptr, m, mem, st));
         c->qdev.ensure((size_t)std::min<int64_t>(m, MFMA_QB) * ix->d * sizeof(float));
-        c->rng_aux.ensure(sizeof(CcAuxH));
-        uint8_t* ad = c->rng_aux.as<uint8_t>();
-        CcAuxH h{};
-        for (int j = 0; j < MFMA_QB; ++j) {
-            h.radius[j] = radius;
-            h.go[j] = 1;
-        }
+        c->rng_aux.ensure(sizeof(RangeAuxHead));
+        RangeAuxHead h{};
+        std::fill(h.radius, h.radius + MFMA_QB, radius);
         // (h outlives every copy from it: each change of h below follows a stream synchronisation)
-        HIP_CHECK(hipMemcpyAsync(ad, &h, sizeof(h), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(c->rng_aux.p, h.radius, sizeof(h.radius), hipMemcpyHostToDevice, st));
         DevEvent e0(hipEventDefault), e1(hipEventDefault), e2(hipEventDefault);
         unsigned long long cnt_h[MFMA_QB];
         for (int64_t q0 = 0; q0 < m; q0 += MFMA_QB) {
@@ -89,64 +77,30 @@ int vs_range_components(vs_index* ix, const vs_sel* sel, float radius, int64_t* 
             ++stt.blocks;
             HIP_CHECK(hipEventRecord(e0, st));
             HIP_CHECK(launch_gather_rows(ix->dtype, ix->data, mem + q0, nqb, ix->d, ix->dpad, c->qdev.as<float>(), st));
-            RangeArgs a{};
-            a.corpus = ix->data;
-            a.d = ix->d;
-            a.dpad = ix->dpad;
-            a.dt = ix->dtype;
-            a.metric = ix->metric;
+            RangeArgs a = range_index_args(ix);
             a.n_valid = n;
             a.q = c->qdev.as<float>();
             a.nq = nqb;
-            a.radius = (const float*)(ad + offsetof(CcAuxH, radius));
-            a.go = nullptr;
+            a.radius = range_aux_radius(c);
             a.cnt = cnt_b;
             a.self = mem + q0;
             a.self_mode = VS_SELF_ABOVE;
             // without a selector the members are the rows themselves: the block's smallest id is q0, and no
             // row below it passes for any of its queries
             a.row0 = sel ? 0 : q0;
-            bool scan = true;
-            if (mode != VS_RANGE_SCAN && range_screen_applies(ix, sel, nqb)) {
-                const ScreenArgs s = range_screen(ix, c, a.q, nqb, a.radius, st);
-                const int ny = std::max(1, std::min(32, 2 * ix->num_cu / nqb));
-                HIP_CHECK(launch_cc_refine(a, parent.as<uint32_t>(), s.glist, s.gcnt, s.lcap, ny, st));
-                std::vector<u64> drop_h((size_t)nqb), thr_h((size_t)nqb);
-                HIP_CHECK(hipMemcpyAsync(drop_h.data(), s.drop, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipMemcpyAsync(thr_h.data(), s.thr0, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                // a workgroup compacted the query's buffer and may have cut rows above the threshold: the list
-                // may be incomplete, so the query's edge counter starts again from zero and the scan answers
-                // it.  The unions its refine made stay: each joined a pair that passes the exact predicate,
-                // and uniting a joined pair again changes nothing (cc_unite), so nothing else needs undoing.
-                scan = false;
-                for (int j = 0; j < nqb; ++j) {
-                    h.go[j] = drop_h[j] > thr_h[j] ? 1 : 0;
-                    if (h.go[j]) {
-                        scan = true;
-                        ++stt.rescanned;
-                        HIP_CHECK(hipMemsetAsync(cnt_b + j, 0, sizeof(unsigned long long), st));
-                    }
-                }
-                if (scan) {
-                    HIP_CHECK(hipMemcpyAsync(ad + offsetof(CcAuxH, go), h.go, sizeof(h.go), hipMemcpyHostToDevice, st));
-                    a.go = (const int*)(ad + offsetof(CcAuxH, go));
-                }
-                stt.tier = VS_RANGE_SCREEN;
-            }
-            HIP_CHECK(hipEventRecord(e1, st));
-            if (scan) {
-                // with a selector the sequence is the tail of its ascending list from the block's own first
-                // position: the entries before it are below every self id of the block
-                const uint32_t* ids = sel ? sel->ids + q0 : nullptr;
-                const int64_t mseq = sel ? m - q0 : 0;
-                const int64_t nseq = sel ? mseq : n - q0;
-                const int64_t ranges = (nseq + kCcScanRows - 1) / kCcScanRows;
-                const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ix->num_cu, ranges));
-                // a short sequence, or few workgroups per CU: deal the queries over slices of the grid
-                const int qy = std::max(1, std::min(nqb, 4 * ix->num_cu / G));
-                HIP_CHECK(launch_cc_scan(a, parent.as<uint32_t>(), G, qy, ids, mseq, st));
-            }
+            // with a selector the scan's sequence is the tail of its ascending list from the block's own first
+            // position: the entries before it are below every self id of the block
+            const RangeTiers t = range_tiers(
+                ix, c, a, h, nqb, sel ? sel->ids + q0 : nullptr, sel ? m - q0 : 0, sel ? m - q0 : n - q0, nullptr, sel,
+                mode, st, e1,
+                [&](const RangeArgs& r, const ScreenArgs& s, int ny) {
+                    HIP_CHECK(launch_cc_refine(r, parent.as<uint32_t>(), s.glist, s.gcnt, s.lcap, ny, st));
+                },
+                [&](const RangeArgs& r, int G, int qy, const uint32_t* ids, int64_t mseq) {
+                    HIP_CHECK(launch_cc_scan(r, parent.as<uint32_t>(), G, qy, ids, mseq, st));
+                });
+            if (t.screened) stt.tier = VS_RANGE_SCREEN;
+            stt.rescanned += t.rescanned;
             HIP_CHECK(hipEventRecord(e2, st));
             HIP_CHECK(hipMemcpyAsync(cnt_h, cnt_b, sizeof(cnt_h[0]) * nqb, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));

@@ -67,86 +67,24 @@ hipError_t launch_db_labels(const DbLabelArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-static bool db_args_ok(const RangeArgs& a) {
-    return a.corpus && a.q && a.radius && a.cnt && a.self && a.nq > 0 && a.nq <= MFMA_QB && a.d > 0 && a.n_valid > 0 &&
-           a.n_valid <= (int64_t)0xFFFFFFFFll && (a.metric == METRIC_IP || a.metric == METRIC_L2) &&
-           a.self_mode == VS_SELF_ABOVE && a.row0 >= 0 && a.row0 < a.n_valid;
+// the range kernels with the degree sink (s.deg set) or the cluster sink
+static bool db_args_ok(const RangeArgs& a, const DbSinkArgs& s) {
+    return a.cnt && a.self && a.nq <= MFMA_QB && a.n_valid <= (int64_t)0xFFFFFFFFll && a.self_mode == VS_SELF_ABOVE &&
+           (s.deg ? !s.parent : (s.parent && s.core && s.best));
 }
-
-template <class SINK, int DT>
-static void launch_db_scan_dt(const RangeArgs& a, const typename SINK::Args& sa, int G, int qy, const uint32_t* ids,
-                              int64_t m, hipStream_t st) {
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = qbytes <= RS_QLDS_MAX;
-    const size_t lds = qlds ? qbytes : 0;
-    const dim3 grid(G, qy), block(FS_THREADS);
-    const bool ip = a.metric == METRIC_IP;
-#define VS_DB_SCAN(M, Q)                                                                                              \
-    do {                                                                                                              \
-        if (ids) hipLaunchKernelGGL((k_range_scan<DT, M, Q, true, true, SINK>), grid, block, lds, st, a, ids, m, sa); \
-        else hipLaunchKernelGGL((k_range_scan<DT, M, Q, false, true, SINK>), grid, block, lds, st, a, ids, m, sa);    \
-    } while (0)
-    if (ip && qlds) VS_DB_SCAN(METRIC_IP, true);
-    else if (ip) VS_DB_SCAN(METRIC_IP, false);
-    else if (qlds) VS_DB_SCAN(METRIC_L2, true);
-    else VS_DB_SCAN(METRIC_L2, false);
-#undef VS_DB_SCAN
-}
-
-template <class SINK>
-static hipError_t db_scan_with(const RangeArgs& a, const typename SINK::Args& sa, int G, int qy, const uint32_t* ids,
-                                 int64_t m, hipStream_t st) {
-    if (!db_args_ok(a) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) || (!ids && m != 0) ||
-        (ids && a.row0 != 0))
-        return hipErrorInvalidValue;
-    if (a.dt == DT_F32) launch_db_scan_dt<SINK, DT_F32>(a, sa, G, qy, ids, m, st);
-    else if (a.dt == DT_BF16) launch_db_scan_dt<SINK, DT_BF16>(a, sa, G, qy, ids, m, st);
-    else if (a.dt == DT_F16) launch_db_scan_dt<SINK, DT_F16>(a, sa, G, qy, ids, m, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-template <class SINK, int DT>
-static void launch_db_refine_dt(const RangeArgs& a, const typename SINK::Args& sa, const u64* glist, const int* gcnt,
-                                int lcap, int ny, hipStream_t st) {
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = qbytes <= RS_QLDS_MAX;
-    const size_t lds = qlds ? qbytes : 0;
-    const dim3 grid(a.nq, ny), block(FS_THREADS);
-    const bool ip = a.metric == METRIC_IP;
-#define VS_DB_REFINE(M, Q) \
-    hipLaunchKernelGGL((k_range_refine<DT, M, Q, true, SINK>), grid, block, lds, st, a, glist, gcnt, lcap, sa)
-    if (ip && qlds) VS_DB_REFINE(METRIC_IP, true);
-    else if (ip) VS_DB_REFINE(METRIC_IP, false);
-    else if (qlds) VS_DB_REFINE(METRIC_L2, true);
-    else VS_DB_REFINE(METRIC_L2, false);
-#undef VS_DB_REFINE
-}
-
-template <class SINK>
-static hipError_t db_refine_with(const RangeArgs& a, const typename SINK::Args& sa, const u64* glist, const int* gcnt,
-                                   int lcap, int ny, hipStream_t st) {
-    if (!db_args_ok(a) || !glist || !gcnt || lcap <= 0 || ny < 1 || ny > 65535) return hipErrorInvalidValue;
-    if (a.dt == DT_BF16) launch_db_refine_dt<SINK, DT_BF16>(a, sa, glist, gcnt, lcap, ny, st);
-    else if (a.dt == DT_F16) launch_db_refine_dt<SINK, DT_F16>(a, sa, glist, gcnt, lcap, ny, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-static bool db_sink_ok(const DbSinkArgs& s) { return s.deg ? !s.parent : (s.parent && s.core && s.best); }
 
 hipError_t launch_db_scan(const RangeArgs& a, const DbSinkArgs& s, int G, int qy, const uint32_t* ids, int64_t m,
                           hipStream_t st) {
-    if (!db_sink_ok(s)) return hipErrorInvalidValue;
-    if (s.deg) return db_scan_with<RsDegreeSink>(a, RsDegreeSink::Args{s.deg}, G, qy, ids, m, st);
-    return db_scan_with<RsDbscanSink>(a, RsDbscanSink::Args{s.parent, s.core, s.best}, G, qy, ids, m, st);
+    if (!db_args_ok(a, s)) return hipErrorInvalidValue;
+    if (s.deg) return rs_launch_scan<RsDegreeSink, true>(a, {s.deg}, 0, 0, G, qy, ids, m, st);
+    return rs_launch_scan<RsDbscanSink, true>(a, {s.parent, s.core, s.best}, 0, 0, G, qy, ids, m, st);
 }
 
 hipError_t launch_db_refine(const RangeArgs& a, const DbSinkArgs& s, const u64* glist, const int* gcnt, int lcap, int ny,
                             hipStream_t st) {
-    if (!db_sink_ok(s)) return hipErrorInvalidValue;
-    if (s.deg) return db_refine_with<RsDegreeSink>(a, RsDegreeSink::Args{s.deg}, glist, gcnt, lcap, ny, st);
-    return db_refine_with<RsDbscanSink>(a, RsDbscanSink::Args{s.parent, s.core, s.best}, glist, gcnt, lcap, ny, st);
+    if (!db_args_ok(a, s)) return hipErrorInvalidValue;
+    if (s.deg) return rs_launch_refine<RsDegreeSink, true>(a, {s.deg}, glist, gcnt, lcap, ny, st);
+    return rs_launch_refine<RsDbscanSink, true>(a, {s.parent, s.core, s.best}, glist, gcnt, lcap, ny, st);
 }
 
 }  // namespace vs

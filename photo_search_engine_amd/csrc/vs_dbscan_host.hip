@@ -3,29 +3,14 @@
 //
 // db_pass is the self-join of the duplicate groups (vs_components_host.hip: members ascending, VS_SELF_ABOVE,
 // blocks of MFMA_QB gathered on the device, the row0 rule or the selector-tail rule) with a sink and a mask of
-// the queries to answer.  vs_range_degrees is pass 1 (degree sink, every query) and a readback;
-// vs_range_dbscan is pass 1, k_db_core, pass 2 (cluster sink, the queries that met an edge in pass 1) and
-// the labels.
-//
-// Exactly once per edge: pass 1 adds, and an add cannot be made twice.  The screen's overflow flags (drop,
-// thr0) are written by range_screen's kernels alone -- launch_pack_qtile zeroes drop, launch_range_thr sets
-// thr0, launch_screen_mfma raises drop; the refine reads glist / gcnt only -- so they are read back before the
-// refine is launched, and refine and scan get complementary masks: a query is answered by one tier.  Pass 2's
-// unions and maxima are idempotent and would not need it; it takes the same road so that there is one.
-#include "vs_walk.h"
+// the queries to answer, through the range search's tiers (range_tiers, vs_range_tiers.h).  vs_range_degrees
+// is pass 1 (degree sink, every query) and a readback; vs_range_dbscan is pass 1, k_db_core, pass 2 (cluster
+// sink, the queries that met an edge in pass 1) and the labels.
+#include "vs_range_tiers.h"
 
 using namespace vs;
 
 namespace {
-
-constexpr int kDbScanRows = 64;  // rows per workgroup of the scan, at least (the range scan's figure)
-
-// the call's small device arrays and their host mirror
-struct DbAuxH {
-    float radius[MFMA_QB];
-    int go_refine[MFMA_QB];
-    int go_scan[MFMA_QB];
-};
 
 struct DbStats {
     int64_t members = 0, edges = 0, clusters = 0, core = 0, border = 0, noise = 0, tier = VS_RANGE_SCAN;
@@ -51,8 +36,7 @@ struct DbCall {
     int mode;
     const int64_t* mem;       // [m] the members' ids, ascending (device)
     unsigned long long* cnt;  // [nblocks][MFMA_QB] pass 1's edges above each query (device)
-    uint8_t* ad;              // DbAuxH (device)
-    DbAuxH h;
+    RangeAuxHead h;           // (the radii are uploaded once per call)
 };
 
 // One pass of the self-join.  active: per member position, whether the query is to be answered (null: all);
@@ -65,79 +49,36 @@ void db_pass(DbCall& k, const DbSinkArgs& sink, const unsigned long long* active
     int64_t block = 0;
     for (int64_t q0 = 0; q0 < k.m; q0 += MFMA_QB, ++block) {
         const int nqb = (int)std::min<int64_t>(MFMA_QB, k.m - q0);
-        int on[MFMA_QB];
-        int non = 0;
-        for (int j = 0; j < nqb; ++j) {
-            on[j] = !active || active[q0 + j] != 0ull ? 1 : 0;
-            non += on[j];
-        }
-        if (non == 0) continue;  // (no gather, no screen, no scan)
+        if (active && std::all_of(active + q0, active + q0 + nqb, [](unsigned long long v) { return v == 0ull; }))
+            continue;  // (no gather, no screen, no scan)
         ++stt.blocks[pass];
         HIP_CHECK(hipEventRecord(e0, st));
         HIP_CHECK(launch_gather_rows(ix->dtype, ix->data, k.mem + q0, nqb, ix->d, ix->dpad, c->qdev.as<float>(), st));
-        RangeArgs a{};
-        a.corpus = ix->data;
-        a.d = ix->d;
-        a.dpad = ix->dpad;
-        a.dt = ix->dtype;
-        a.metric = ix->metric;
+        RangeArgs a = range_index_args(ix);
         a.n_valid = k.n;
         a.q = c->qdev.as<float>();
         a.nq = nqb;
-        a.radius = (const float*)(k.ad + offsetof(DbAuxH, radius));
+        a.radius = range_aux_radius(c);
         a.cnt = k.cnt + block * MFMA_QB;
         a.self = k.mem + q0;
         a.self_mode = VS_SELF_ABOVE;
         // without a selector the members are the rows themselves: the block's smallest id is q0, and no
         // row below it passes for any of its queries
         a.row0 = k.sel ? 0 : q0;
-        bool refine = false, scan = true;
-        ScreenArgs s{};
-        for (int j = 0; j < MFMA_QB; ++j) {
-            k.h.go_refine[j] = 0;
-            k.h.go_scan[j] = j < nqb ? on[j] : 0;
-        }
-        if (k.mode != VS_RANGE_SCAN && range_screen_applies(ix, k.sel, nqb)) {
-            s = range_screen(ix, c, a.q, nqb, a.radius, st);
-            std::vector<u64> drop_h((size_t)nqb), thr_h((size_t)nqb);
-            HIP_CHECK(hipMemcpyAsync(drop_h.data(), s.drop, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipMemcpyAsync(thr_h.data(), s.thr0, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            // a workgroup compacted the query's buffer and may have cut rows above the threshold: the list may
-            // be incomplete, so the scan answers the query and the refine leaves it alone
-            scan = false;
-            for (int j = 0; j < nqb; ++j) {
-                const bool over = drop_h[j] > thr_h[j];
-                k.h.go_refine[j] = on[j] && !over ? 1 : 0;
-                k.h.go_scan[j] = on[j] && over ? 1 : 0;
-                refine = refine || k.h.go_refine[j];
-                scan = scan || k.h.go_scan[j];
-                stt.rescanned[pass] += k.h.go_scan[j];
-            }
-            stt.tier = VS_RANGE_SCREEN;
-        }
+        // with a selector the scan's sequence is the tail of its ascending list from the block's own first
+        // position: the entries before it are below every self id of the block
         // (k.h outlives the copy from it: the block ends with a stream synchronisation)
-        HIP_CHECK(hipMemcpyAsync(k.ad + offsetof(DbAuxH, go_refine), k.h.go_refine, 2 * sizeof(k.h.go_refine),
-                                 hipMemcpyHostToDevice, st));
-        if (refine) {
-            a.go = (const int*)(k.ad + offsetof(DbAuxH, go_refine));
-            const int ny = std::max(1, std::min(32, 2 * ix->num_cu / nqb));
-            HIP_CHECK(launch_db_refine(a, sink, s.glist, s.gcnt, s.lcap, ny, st));
-        }
-        HIP_CHECK(hipEventRecord(e1, st));
-        if (scan) {
-            a.go = (const int*)(k.ad + offsetof(DbAuxH, go_scan));
-            // with a selector the sequence is the tail of its ascending list from the block's own first
-            // position: the entries before it are below every self id of the block
-            const uint32_t* ids = k.sel ? k.sel->ids + q0 : nullptr;
-            const int64_t mseq = k.sel ? k.m - q0 : 0;
-            const int64_t nseq = k.sel ? mseq : k.n - q0;
-            const int64_t ranges = (nseq + kDbScanRows - 1) / kDbScanRows;
-            const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ix->num_cu, ranges));
-            // a short sequence, or few workgroups per CU: deal the queries over slices of the grid
-            const int qy = std::max(1, std::min(nqb, 4 * ix->num_cu / G));
-            HIP_CHECK(launch_db_scan(a, sink, G, qy, ids, mseq, st));
-        }
+        const RangeTiers t = range_tiers(
+            ix, c, a, k.h, nqb, k.sel ? k.sel->ids + q0 : nullptr, k.sel ? k.m - q0 : 0, k.sel ? k.m - q0 : k.n - q0,
+            active ? active + q0 : nullptr, k.sel, k.mode, st, e1,
+            [&](const RangeArgs& r, const ScreenArgs& s, int ny) {
+                HIP_CHECK(launch_db_refine(r, sink, s.glist, s.gcnt, s.lcap, ny, st));
+            },
+            [&](const RangeArgs& r, int G, int qy, const uint32_t* ids, int64_t mseq) {
+                HIP_CHECK(launch_db_scan(r, sink, G, qy, ids, mseq, st));
+            });
+        if (t.screened) stt.tier = VS_RANGE_SCREEN;
+        stt.rescanned[pass] += t.rescanned;
         HIP_CHECK(hipEventRecord(e2, st));
         HIP_CHECK(hipStreamSynchronize(st));
         stt.ms[2 * pass] += ms_between(e0, e1);
@@ -196,10 +137,9 @@ void db_run(vs_index* ix, const vs_sel* sel, float radius, int64_t min_samples, 
     HIP_CHECK(launch_km_members(sel_ids, m, c->row_ids.as<int64_t>(), st));
     k.mem = c->row_ids.as<int64_t>();
     c->qdev.ensure((size_t)std::min<int64_t>(m, MFMA_QB) * ix->d * sizeof(float));
-    c->rng_aux.ensure(sizeof(DbAuxH));
-    k.ad = c->rng_aux.as<uint8_t>();
-    for (int j = 0; j < MFMA_QB; ++j) k.h.radius[j] = radius;
-    HIP_CHECK(hipMemcpyAsync(k.ad, k.h.radius, sizeof(k.h.radius), hipMemcpyHostToDevice, st));
+    c->rng_aux.ensure(sizeof(RangeAuxHead));
+    std::fill(k.h.radius, k.h.radius + MFMA_QB, radius);
+    HIP_CHECK(hipMemcpyAsync(c->rng_aux.p, k.h.radius, sizeof(k.h.radius), hipMemcpyHostToDevice, st));
 
     // pass 1: the degrees, and each query's edges above
     DbSinkArgs s1{};

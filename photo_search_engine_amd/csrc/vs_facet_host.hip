@@ -3,24 +3,15 @@
 //
 // Queries are staged in blocks as the range search stages them; a block's answers are one table of
 // nqb x bins 64-bit counters on the device, zeroed before the block, read back after it and widened into
-// the caller's counts / totals.  The SCREEN tier is the range search's (range_screen, then the refine with
-// the count sink); a query whose survivor list a workgroup had to cut gets its row of the table zeroed and
-// is re-answered by the scan, so no query is counted from an incomplete list and no row twice.
-#include "vs_walk.h"
+// the caller's counts / totals.  The tiers are the range search's (range_tiers, vs_range_tiers.h) with the
+// count sink.
+#include "vs_range_tiers.h"
 
 using namespace vs;
 
 namespace {
 
-constexpr int kFacetScanRows = 64;  // rows per workgroup of the scan, at least (the range scan's figure)
-
 std::atomic<int64_t> g_facet_staging{64ll << 20};  // vs_set_facet_staging_bytes
-
-// the block's small device arrays and their host mirror
-struct FacetAuxH {
-    float radius[MFMA_QB];
-    int go[MFMA_QB];
-};
 
 struct FacetStats {
     int64_t total = 0, tier = VS_RANGE_SCAN, rescanned = 0, form = 0, blocks = 0;
@@ -88,76 +79,43 @@ int vs_range_count(vs_index* ix, const vs_groups* gr, const vs_sel* sel, const f
         DevBuf table;  // (freed when the call returns)
         table.ensure((size_t)std::min<int64_t>(qb, nq) * row_bytes);
         std::vector<unsigned long long> table_h((size_t)std::min<int64_t>(qb, nq) * bins);
-        c->rng_aux.ensure(sizeof(FacetAuxH));
-        uint8_t* ad = c->rng_aux.as<uint8_t>();
-        FacetAuxH h{};
+        c->rng_aux.ensure(sizeof(RangeAuxHead));
+        RangeAuxHead h{};
         DevEvent e0(hipEventDefault), e1(hipEventDefault), e2(hipEventDefault), e3(hipEventDefault);
-        // the sequence the scan's workgroups split, as range_block sizes it
+        // the sequence the scan's workgroups split
         const int64_t nseq = sel ? sel->m : n_cov;
-        const int64_t ranges = (nseq + kFacetScanRows - 1) / kFacetScanRows;
-        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ix->num_cu, ranges));
+        const int G = range_scan_grid(ix->num_cu, nseq, 1).G;
         const bool lds = facet_lds_form(form, bins, (nseq + G - 1) / G);
         for (int64_t q0 = 0; q0 < nq; q0 += qb) {
             const int nqb = (int)std::min<int64_t>(qb, nq - q0);
             ++stt.blocks;
             // (the previous block synchronised the stream after its copies from hq and h)
             stage_queries(ix, c, q, q0, nqb, st);
-            for (int j = 0; j < nqb; ++j) {
-                h.radius[j] = radius[q0 + j];
-                h.go[j] = 1;
-            }
-            HIP_CHECK(hipMemcpyAsync(ad, &h, sizeof(h), hipMemcpyHostToDevice, st));
+            std::copy(radius + q0, radius + q0 + nqb, h.radius);
+            HIP_CHECK(hipMemcpyAsync(c->rng_aux.p, h.radius, sizeof(h.radius), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemsetAsync(table.p, 0, (size_t)nqb * row_bytes, st));
-            RangeArgs a{};
-            a.corpus = ix->data;
-            a.d = ix->d;
-            a.dpad = ix->dpad;
-            a.dt = ix->dtype;
-            a.metric = ix->metric;
+            RangeArgs a = range_index_args(ix);
             a.n_valid = n_cov;  // (rows behind the groups are no members: not scanned, not refined)
             a.q = c->qdev.as<float>();
             a.nq = nqb;
-            a.radius = (const float*)(ad + offsetof(FacetAuxH, radius));
-            a.go = (const int*)(ad + offsetof(FacetAuxH, go));
-            a.self_mode = VS_SELF_KEEP;
+            a.radius = range_aux_radius(c);
             FacetArgs f{};
             f.gid = gr ? gr->gid.as<int32_t>() : nullptr;
             f.n_cov = n_cov;
             f.bins = (int)bins;
             f.hist = table.as<unsigned long long>();
-            bool scan = true;
             HIP_CHECK(hipEventRecord(e0, st));
-            if (mode != VS_RANGE_SCAN && range_screen_applies(ix, sel, nqb)) {
-                const ScreenArgs s = range_screen(ix, c, a.q, nqb, a.radius, st);
-                RangeArgs r = a;
-                r.go = nullptr;
-                const int ny = std::max(1, std::min(32, 2 * ix->num_cu / nqb));
-                HIP_CHECK(launch_facet_refine(r, f, s.glist, s.gcnt, s.lcap, ny, st));
-                std::vector<u64> drop_h((size_t)nqb), thr_h((size_t)nqb);
-                HIP_CHECK(hipMemcpyAsync(drop_h.data(), s.drop, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipMemcpyAsync(thr_h.data(), s.thr0, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                // a workgroup compacted the query's buffer and may have cut rows above the threshold: the
-                // list may be incomplete, so the row starts again from zero and the scan answers it
-                scan = false;
-                for (int j = 0; j < nqb; ++j) {
-                    h.go[j] = drop_h[j] > thr_h[j] ? 1 : 0;
-                    if (h.go[j]) {
-                        scan = true;
-                        ++stt.rescanned;
-                        HIP_CHECK(hipMemsetAsync((uint8_t*)table.p + (size_t)j * row_bytes, 0, (size_t)row_bytes, st));
-                    }
-                }
-                if (scan) HIP_CHECK(hipMemcpyAsync(ad, &h, sizeof(h), hipMemcpyHostToDevice, st));
-                stt.tier = VS_RANGE_SCREEN;
-            }
-            HIP_CHECK(hipEventRecord(e1, st));
-            if (scan) {
-                // a short sequence, or few workgroups per CU: deal the queries over slices of the grid
-                const int qy = std::max(1, std::min(nqb, 4 * ix->num_cu / G));
-                HIP_CHECK(launch_facet_scan(a, f, lds, G, qy, sel ? sel->ids : nullptr, sel ? sel->m : 0, st));
-                stt.form = lds ? VS_FACET_HIST_LDS : VS_FACET_HIST_GLOBAL;
-            }
+            const RangeTiers t = range_tiers(
+                ix, c, a, h, nqb, sel ? sel->ids : nullptr, sel ? sel->m : 0, nseq, nullptr, sel, mode, st, e1,
+                [&](const RangeArgs& r, const ScreenArgs& s, int ny) {
+                    HIP_CHECK(launch_facet_refine(r, f, s.glist, s.gcnt, s.lcap, ny, st));
+                },
+                [&](const RangeArgs& r, int g, int qy, const uint32_t* ids, int64_t m) {
+                    HIP_CHECK(launch_facet_scan(r, f, lds, g, qy, ids, m, st));
+                });
+            if (t.screened) stt.tier = VS_RANGE_SCREEN;
+            stt.rescanned += t.rescanned;
+            if (t.scanned) stt.form = lds ? VS_FACET_HIST_LDS : VS_FACET_HIST_GLOBAL;
             HIP_CHECK(hipEventRecord(e2, st));
             HIP_CHECK(hipMemcpyAsync(table_h.data(), table.p, (size_t)nqb * row_bytes, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipEventRecord(e3, st));

@@ -2,7 +2,8 @@
 // (vs_store.hip, vs_search.hip, vs_sel_host.hip, vs_range_host.hip, vs_rows_host.hip, vs_probe.hip,
 // vs_api.hip, vs_remove.hip, vs_kmeans.hip, vs_diverse_host.hip, vs_group_host.hip, vs_adjust_host.hip,
 // vs_fuse_host.hip, vs_after_host.hip, vs_facet_host.hip, vs_components_host.hip, vs_scoresel_host.hip, vs_dbscan_host.hip; the
-// five before the last three share the list-deepening driver of vs_walk.h).
+// five before the last four share the list-deepening driver of vs_walk.h; vs_range_host.hip and the last four
+// share the tier driver of vs_range_tiers.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -32,49 +32,16 @@
 namespace vs {
 
 // ---- SCAN tier ------------------------------------------------------------------------------------
-// (k_range_scan and k_range_refine: vs_range_scan.h, here with the pair sink)
-template <int DT, int METRIC, bool QLDS>
-static void launch_range_scan_one(const RangeArgs& a, int G, int qy, size_t lds, const uint32_t* ids, int64_t m,
-                                  hipStream_t st) {
-    const bool self = a.self_mode != VS_SELF_KEEP;
-    const dim3 grid(G, qy), block(FS_THREADS);
-    const RsPairSink::Args sa{};
-    if (ids && self) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true, true>), grid, block, lds, st, a, ids, m, sa);
-    else if (ids) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, true, false>), grid, block, lds, st, a, ids, m, sa);
-    else if (self) hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false, true>), grid, block, lds, st, a, ids, m, sa);
-    else hipLaunchKernelGGL((k_range_scan<DT, METRIC, QLDS, false, false>), grid, block, lds, st, a, ids, m, sa);
-}
-
-template <int DT>
-static void launch_range_scan_dt(const RangeArgs& a, int G, int qy, const uint32_t* ids, int64_t m, hipStream_t st) {
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = qbytes <= RS_QLDS_MAX;
-    const size_t lds = qlds ? qbytes : 0;
-    if (a.metric == METRIC_IP) {
-        if (qlds) launch_range_scan_one<DT, METRIC_IP, true>(a, G, qy, lds, ids, m, st);
-        else launch_range_scan_one<DT, METRIC_IP, false>(a, G, qy, lds, ids, m, st);
-    } else {
-        if (qlds) launch_range_scan_one<DT, METRIC_L2, true>(a, G, qy, lds, ids, m, st);
-        else launch_range_scan_one<DT, METRIC_L2, false>(a, G, qy, lds, ids, m, st);
-    }
-}
-
-static bool range_args_ok(const RangeArgs& a) {
-    return a.corpus && a.q && a.radius && a.off && a.cap && a.cnt && a.psc && a.pid && a.nq > 0 && a.d > 0 &&
-           a.n_valid > 0 && (a.metric == METRIC_IP || a.metric == METRIC_L2) &&
-           (a.self_mode == VS_SELF_KEEP || ((a.self_mode == VS_SELF_DROP || a.self_mode == VS_SELF_ABOVE) && a.self)) &&
-           a.row0 >= 0 && a.row0 < a.n_valid;
+// (k_range_scan, k_range_refine and their launchers: vs_range_scan.h, here with the pair sink)
+static bool pair_args_ok(const RangeArgs& a) {
+    return a.off && a.cap && a.cnt && a.psc && a.pid &&
+           (a.self_mode == VS_SELF_KEEP || ((a.self_mode == VS_SELF_DROP || a.self_mode == VS_SELF_ABOVE) && a.self));
 }
 
 hipError_t launch_range_scan(const RangeArgs& a, int G, int qy, const uint32_t* ids, int64_t m, hipStream_t st) {
-    if (!range_args_ok(a) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) || (!ids && m != 0) ||
-        (ids && a.row0 != 0))
-        return hipErrorInvalidValue;
-    if (a.dt == DT_F32) launch_range_scan_dt<DT_F32>(a, G, qy, ids, m, st);
-    else if (a.dt == DT_BF16) launch_range_scan_dt<DT_BF16>(a, G, qy, ids, m, st);
-    else if (a.dt == DT_F16) launch_range_scan_dt<DT_F16>(a, G, qy, ids, m, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (!pair_args_ok(a)) return hipErrorInvalidValue;
+    if (a.self_mode != VS_SELF_KEEP) return rs_launch_scan<RsPairSink, true>(a, {}, 0, 0, G, qy, ids, m, st);
+    return rs_launch_scan<RsPairSink, false>(a, {}, 0, 0, G, qy, ids, m, st);
 }
 
 // ---- SCREEN tier: the starting threshold ------------------------------------------------------------
@@ -131,34 +98,11 @@ hipError_t launch_range_thr(int metric, const float* radius, const float* qinfo,
 }
 
 // ---- SCREEN tier: exact refine of the survivors ------------------------------------------------------
-template <int DT>
-static void launch_range_refine_dt(const RangeArgs& a, const u64* glist, const int* gcnt, int lcap, int ny,
-                                   hipStream_t st) {
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = qbytes <= RS_QLDS_MAX;
-    const size_t lds = qlds ? qbytes : 0;
-    const dim3 grid(a.nq, ny), block(FS_THREADS);
-    const bool ip = a.metric == METRIC_IP, self = a.self_mode != VS_SELF_KEEP;
-    const RsPairSink::Args sa{};
-#define VS_RANGE_REFINE(M, Q, S) hipLaunchKernelGGL((k_range_refine<DT, M, Q, S>), grid, block, lds, st, a, glist, gcnt, lcap, sa)
-    if (ip && qlds && self) VS_RANGE_REFINE(METRIC_IP, true, true);
-    else if (ip && qlds) VS_RANGE_REFINE(METRIC_IP, true, false);
-    else if (ip && self) VS_RANGE_REFINE(METRIC_IP, false, true);
-    else if (ip) VS_RANGE_REFINE(METRIC_IP, false, false);
-    else if (qlds && self) VS_RANGE_REFINE(METRIC_L2, true, true);
-    else if (qlds) VS_RANGE_REFINE(METRIC_L2, true, false);
-    else if (self) VS_RANGE_REFINE(METRIC_L2, false, true);
-    else VS_RANGE_REFINE(METRIC_L2, false, false);
-#undef VS_RANGE_REFINE
-}
-
 hipError_t launch_range_refine(const RangeArgs& a, const u64* glist, const int* gcnt, int lcap, int ny,
                                hipStream_t st) {
-    if (!range_args_ok(a) || !glist || !gcnt || lcap <= 0 || ny < 1 || ny > 65535) return hipErrorInvalidValue;
-    if (a.dt == DT_BF16) launch_range_refine_dt<DT_BF16>(a, glist, gcnt, lcap, ny, st);
-    else if (a.dt == DT_F16) launch_range_refine_dt<DT_F16>(a, glist, gcnt, lcap, ny, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (!pair_args_ok(a)) return hipErrorInvalidValue;
+    if (a.self_mode != VS_SELF_KEEP) return rs_launch_refine<RsPairSink, true>(a, {}, glist, gcnt, lcap, ny, st);
+    return rs_launch_refine<RsPairSink, false>(a, {}, glist, gcnt, lcap, ny, st);
 }
 
 // ---- emit ------------------------------------------------------------------------------------------

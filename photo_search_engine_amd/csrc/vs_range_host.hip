@@ -1,5 +1,5 @@
 // vs_range_host.hip -- host side of range search (include/vs.h "range search"; kernels: vs_range.hip).
-#include "vs_index.h"
+#include "vs_range_tiers.h"
 
 using namespace vs;
 
@@ -7,17 +7,17 @@ namespace {
 
 // the block's small device arrays and their host mirror (one upload of the leading part per launch)
 struct RangeAuxH {
-    float radius[MFMA_QB];
-    int go[MFMA_QB];
+    RangeAuxHead head;
     unsigned long long cnt[MFMA_QB];
     int64_t off[MFMA_QB];
     int64_t cap[MFMA_QB];
     RangeSeg seg[MFMA_QB];
 };
-static_assert(sizeof(RangeSeg) == 32 && offsetof(RangeAuxH, seg) == 8192, "RangeAuxH layout");
+static_assert(sizeof(RangeSeg) == 32 && offsetof(RangeAuxH, head) == 0 && offsetof(RangeAuxH, cnt) == 3072 &&
+                  offsetof(RangeAuxH, seg) == 9216,
+              "RangeAuxH layout");
 
 constexpr int64_t kRangePairBytes = 32ll << 20;  // first-pass pair buffer of one block (12 B per pair)
-constexpr int kRangeScanRows = 64;               // rows per workgroup of the scan, at least
 
 }  // namespace
 
@@ -61,25 +61,18 @@ void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int n
     uint8_t* ad = c->rng_aux.as<uint8_t>();
     c->rng_p[0].ensure((size_t)std::max<int64_t>(1, capq * nqb) * 12);
     for (int q = 0; q < nqb; ++q) {
-        h.radius[q] = rad[q];
-        h.go[q] = 1;
+        h.head.radius[q] = rad[q];
         h.cnt[q] = 0;
         h.off[q] = (int64_t)q * capq;
         h.cap[q] = capq;
     }
     // (h outlives every copy from it: each change of h below follows a stream synchronisation)
     HIP_CHECK(hipMemcpyAsync(ad, &h, offsetof(RangeAuxH, seg), hipMemcpyHostToDevice, st));
-    RangeArgs a{};
-    a.corpus = ix->data;
-    a.d = ix->d;
-    a.dpad = ix->dpad;
-    a.dt = ix->dtype;
-    a.metric = ix->metric;
+    RangeArgs a = range_index_args(ix);
     a.n_valid = ix->ntotal;
     a.q = qd;
     a.nq = nqb;
-    a.radius = (const float*)(ad + offsetof(RangeAuxH, radius));
-    a.go = (const int*)(ad + offsetof(RangeAuxH, go));
+    a.radius = range_aux_radius(c);
     a.cnt = (unsigned long long*)(ad + offsetof(RangeAuxH, cnt));
     a.off = (const int64_t*)(ad + offsetof(RangeAuxH, off));
     a.cap = (const int64_t*)(ad + offsetof(RangeAuxH, cap));
@@ -91,41 +84,38 @@ void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int n
     auto read_counts = [&] {
         HIP_CHECK(hipMemcpyAsync(h.cnt, a.cnt, sizeof(h.cnt[0]) * nqb, hipMemcpyDeviceToHost, st));
     };
+    // The pair sink has a second reason to give a query to the scan, known only after the refine: its passing
+    // rows outgrew its region.  Its counters have to be read after the refine in any case, so the block does not
+    // take range_tiers (which would put a second synchronisation before the refine): every query is refined, the
+    // flags come back with the counters, and the scan answers the cut and the outgrown queries from a counter
+    // set back to zero -- the pair sink's own redo, its region is simply written again.
     std::vector<char> need((size_t)nqb, 1);
     int64_t total2 = 0;  // pairs of the second buffer (reruns)
     if (screen) {
+        RangeCut flags;
         const ScreenArgs s = range_screen(ix, c, qd, nqb, a.radius, st);
-        RangeArgs r = a;
-        r.go = nullptr;
-        const int ny = std::max(1, std::min(32, 2 * ix->num_cu / nqb));
-        HIP_CHECK(launch_range_refine(r, s.glist, s.gcnt, s.lcap, ny, st));
-        std::vector<u64> drop_h((size_t)nqb), thr_h((size_t)nqb);
+        HIP_CHECK(launch_range_refine(a, s.glist, s.gcnt, s.lcap, range_refine_ny(ix->num_cu, nqb), st));
         read_counts();
-        HIP_CHECK(hipMemcpyAsync(drop_h.data(), s.drop, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipMemcpyAsync(thr_h.data(), s.thr0, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
+        flags.read(s, nqb, st);
         HIP_CHECK(hipStreamSynchronize(st));
-        // overflow: a workgroup compacted the query's buffer and may have cut rows above the
-        // threshold -- its list may be incomplete, so the scan answers it (as does a query whose
-        // passing rows outgrew its region)
         for (int q = 0; q < nqb; ++q) {
-            need[q] = (drop_h[q] > thr_h[q] || (!count_only && (int64_t)h.cnt[q] > capq)) ? 1 : 0;
+            need[q] = (flags.cut(q) || (!count_only && (int64_t)h.cnt[q] > capq)) ? 1 : 0;
             stt.rescanned += need[q];
         }
         stt.tier = VS_RANGE_SCREEN;
     }
     if (std::any_of(need.begin(), need.end(), [](char v) { return v != 0; })) {
         for (int q = 0; q < nqb; ++q) {
-            h.go[q] = need[q];
+            h.head.go_scan[q] = need[q];
             if (need[q]) h.cnt[q] = 0;
         }
-        HIP_CHECK(hipMemcpyAsync(ad, &h, offsetof(RangeAuxH, off), hipMemcpyHostToDevice, st));
-        const int64_t ranges = (nseq + kRangeScanRows - 1) / kRangeScanRows;
-        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ix->num_cu, ranges));
-        // a short sequence, or few workgroups per CU: deal the queries over slices of the grid
-        const int qy = std::max(1, std::min(nqb, 4 * ix->num_cu / G));
+        HIP_CHECK(hipMemcpyAsync(ad + offsetof(RangeAuxHead, go_scan), h.head.go_scan,
+                                 offsetof(RangeAuxH, off) - offsetof(RangeAuxHead, go_scan), hipMemcpyHostToDevice, st));
+        a.go = (const int*)(ad + offsetof(RangeAuxHead, go_scan));
+        const RangeScanGrid g = range_scan_grid(ix->num_cu, nseq, nqb);
         const uint32_t* ids = sel ? sel->ids : nullptr;
         const int64_t m = sel ? sel->m : 0;
-        HIP_CHECK(launch_range_scan(a, G, qy, ids, m, st));
+        HIP_CHECK(launch_range_scan(a, g.G, g.qy, ids, m, st));
         read_counts();
         HIP_CHECK(hipStreamSynchronize(st));
         std::vector<int> over;
@@ -134,10 +124,10 @@ void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int n
                 if (need[q] && (int64_t)h.cnt[q] > capq) over.push_back(q);
         if (!over.empty()) {
             std::vector<int64_t> want((size_t)nqb, 0);
-            for (int q = 0; q < nqb; ++q) h.go[q] = 0;
+            for (int q = 0; q < nqb; ++q) h.head.go_scan[q] = 0;
             for (int q : over) {
                 want[q] = (int64_t)h.cnt[q];
-                h.go[q] = 1;
+                h.head.go_scan[q] = 1;
                 h.cnt[q] = 0;
                 h.off[q] = total2;
                 h.cap[q] = want[q];
@@ -149,7 +139,7 @@ void range_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* qd, int n
             RangeArgs a2 = a;
             a2.psc = c->rng_p[1].as<double>();
             a2.pid = (uint32_t*)(a2.psc + total2);
-            HIP_CHECK(launch_range_scan(a2, G, qy, ids, m, st));
+            HIP_CHECK(launch_range_scan(a2, g.G, g.qy, ids, m, st));
             read_counts();
             HIP_CHECK(hipStreamSynchronize(st));
             for (int q : over)

@@ -11,8 +11,10 @@
 //   put<..>(..)      lane 0 of a wave: its R scored rows
 //   close(q, tid)    every thread, after the query's last row (the next query's first barrier follows)
 // The pair sink's open / close are empty and take no barrier: a plain range search compiles to the code
-// it always ran.
+// it always ran.  The launchers of both kernels, for any sink, are at the end of the file.
 #pragma once
+#include <type_traits>
+
 #include "vs_scan.h"
 
 namespace vs {
@@ -231,7 +233,7 @@ struct RsUnionSink {
 // pass 1, the neighbour counts: an edge (self, id) is one neighbour more for either end.  The wave-step's
 // passing rows go to the block's cnt[q] with one atomic (the query's "edges above", which pass 2 reads to
 // skip the queries that meet none), to deg[self] with one more, and each passing row's deg[id] gets 1.
-// An add is not idempotent: the host gives every query to exactly one tier (vs_dbscan_host.hip).
+// An add is not idempotent: the host gives every query to exactly one tier (range_tiers, vs_range_tiers.h).
 struct RsDegreeSink {
     struct Args {
         uint32_t* deg;  // [n_valid], zeroed by the host
@@ -323,8 +325,8 @@ struct RsDbscanSink {
 // words (ALL): one bitmap per query of the block.  The rows of a wave-step are FS_NW apart, so several
 // usually fall into one 64-bit word: their bits are merged, and per distinct word of a shared bitmap one
 // relaxed agent-scope load decides whether an atomicOr is still needed (with many queries most are not).
-// Bits only ever get set, so a stale load costs an atomic and never a bit, and setting a bit twice changes
-// nothing: a query re-answered by the scan after its refine needs no clearing.  Ids index bits[0, ceil(n_valid / 64)) only: put() bounds them again.
+// Bits only ever get set, so a stale load costs an atomic and never a bit.  Ids index
+// bits[0, ceil(n_valid / 64)) only: put() bounds them again.
 struct RsBitSink {
     struct Args {
         unsigned long long* bits;
@@ -463,6 +465,81 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_refine(RangeArgs a, const 
         exact_score_rows<DT, METRIC, QLDS, RR>(a.corpus, rr, qs, qv, a.d, a.dpad, lane, s);
         if (lane == 0) sink.template put<METRIC, RR, SELF>(a, q, rq, sq, self, rr, s);
     }
+}
+
+// ---- launchers -------------------------------------------------------------------------------------
+// One scan launcher and one refine launcher for every sink: the argument checks that no sink changes, the
+// staged query's LDS rule and the dtype x metric x QLDS (x SEL) dispatch.  What a sink adds stays in its own
+// .hip file, in the launch_*_scan / launch_*_refine wrapper of vs_internal.h: its SELF, the check of its own
+// arguments, and (the count sink's LDS form alone) sink_lds, the bytes of dynamic LDS it takes behind the
+// query, with lds_attr, the dynamic LDS limit its kernels are raised to (0: the default limit serves).
+
+// the staged query's bytes of dynamic LDS; 0: the query is too long and stays in global memory (QLDS false)
+inline size_t rs_query_lds(int d) {
+    const size_t qbytes = (size_t)((d + 7) >> 3) * 64;
+    return qbytes <= RS_QLDS_MAX ? qbytes : 0;
+}
+
+inline bool rs_args_ok(const RangeArgs& a) {
+    return a.corpus && a.q && a.radius && a.nq > 0 && a.d > 0 && a.n_valid > 0 &&
+           (a.metric == METRIC_IP || a.metric == METRIC_L2) && a.row0 >= 0 && a.row0 < a.n_valid;
+}
+
+// fn(dt, metric, qlds), the three as integral constants, for the block's dtype, metric and query length;
+// false: the dtype has no kernel (F32: whether fp32 rows have one -- the screen, hence the refine, has none)
+template <bool F32, class FN>
+bool rs_dispatch(const RangeArgs& a, FN&& fn) {
+    const bool qlds = rs_query_lds(a.d) != 0;
+    auto with_dt = [&](auto dt) {
+        auto with_metric = [&](auto metric) {
+            if (qlds) fn(dt, metric, std::true_type{});
+            else fn(dt, metric, std::false_type{});
+        };
+        if (a.metric == METRIC_IP) with_metric(std::integral_constant<int, METRIC_IP>{});
+        else with_metric(std::integral_constant<int, METRIC_L2>{});
+        return true;
+    };
+    if constexpr (F32) {
+        if (a.dt == DT_F32) return with_dt(std::integral_constant<int, DT_F32>{});
+    }
+    if (a.dt == DT_BF16) return with_dt(std::integral_constant<int, DT_BF16>{});
+    if (a.dt == DT_F16) return with_dt(std::integral_constant<int, DT_F16>{});
+    return false;
+}
+
+template <class SINK, bool SELF>
+hipError_t rs_launch_scan(const RangeArgs& a, const typename SINK::Args& sa, size_t sink_lds, int lds_attr, int G, int qy,
+                          const uint32_t* ids, int64_t m, hipStream_t st) {
+    if (!rs_args_ok(a) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) || (!ids && m != 0) ||
+        (ids && a.row0 != 0))
+        return hipErrorInvalidValue;
+    const size_t lds = rs_query_lds(a.d) + sink_lds;
+    const dim3 grid(G, qy), block(FS_THREADS);
+    auto launch = [&](auto kernel) {
+        if (lds_attr) set_lds_attr((const void*)kernel, lds_attr);
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, a, ids, m, sa);
+    };
+    const bool known = rs_dispatch<true>(a, [&](auto dt, auto metric, auto qlds) {
+        constexpr int DT = decltype(dt)::value, METRIC = decltype(metric)::value;
+        constexpr bool QLDS = decltype(qlds)::value;
+        if (ids) launch(k_range_scan<DT, METRIC, QLDS, true, SELF, SINK>);
+        else launch(k_range_scan<DT, METRIC, QLDS, false, SELF, SINK>);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+template <class SINK, bool SELF>
+hipError_t rs_launch_refine(const RangeArgs& a, const typename SINK::Args& sa, const u64* glist, const int* gcnt,
+                            int lcap, int ny, hipStream_t st) {
+    if (!rs_args_ok(a) || !glist || !gcnt || lcap <= 0 || ny < 1 || ny > 65535) return hipErrorInvalidValue;
+    const size_t lds = rs_query_lds(a.d);
+    const dim3 grid(a.nq, ny), block(FS_THREADS);
+    const bool known = rs_dispatch<false>(a, [&](auto dt, auto metric, auto qlds) {
+        constexpr int DT = decltype(dt)::value, METRIC = decltype(metric)::value;
+        constexpr bool QLDS = decltype(qlds)::value;
+        hipLaunchKernelGGL((k_range_refine<DT, METRIC, QLDS, SELF, SINK>), grid, block, lds, st, a, glist, gcnt, lcap, sa);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vs

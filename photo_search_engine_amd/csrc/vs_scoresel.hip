@@ -15,74 +15,21 @@
 
 namespace vs {
 
-template <int DT, int METRIC, bool QLDS, bool SEL>
-constexpr auto k_bits_scan = k_range_scan<DT, METRIC, QLDS, SEL, false, RsBitSink>;
-template <int DT, int METRIC, bool QLDS>
-constexpr auto k_bits_refine = k_range_refine<DT, METRIC, QLDS, false, RsBitSink>;
-
 static bool bits_args_ok(const RangeArgs& a, const BitsArgs& b) {
-    const int64_t nwords = (a.n_valid + 63) >> 6;
-    return a.corpus && a.q && a.radius && a.nq > 0 && a.d > 0 && a.n_valid > 0 &&
-           (a.metric == METRIC_IP || a.metric == METRIC_L2) && a.self_mode == VS_SELF_KEEP && a.row0 == 0 && b.bits &&
-           (b.stride_words == 0 || b.stride_words >= nwords);
-}
-
-template <int DT>
-static void launch_bits_scan_dt(const RangeArgs& a, const BitsArgs& b, int G, int qy, const uint32_t* ids, int64_t m,
-                                hipStream_t st) {
-    const size_t qb = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = qb <= RS_QLDS_MAX;
-    const size_t lds = qlds ? qb : 0;
-    const bool ip = a.metric == METRIC_IP;
-    const dim3 grid(G, qy), block(FS_THREADS);
-    const RsBitSink::Args sa{b.bits, b.stride_words};
-#define VS_BITS_SCAN(M, Q)                                                                                      \
-    do {                                                                                                        \
-        if (ids) hipLaunchKernelGGL((k_bits_scan<DT, M, Q, true>), grid, block, lds, st, a, ids, m, sa);        \
-        else hipLaunchKernelGGL((k_bits_scan<DT, M, Q, false>), grid, block, lds, st, a, ids, m, sa);           \
-    } while (0)
-    if (ip && qlds) VS_BITS_SCAN(METRIC_IP, true);
-    else if (ip) VS_BITS_SCAN(METRIC_IP, false);
-    else if (qlds) VS_BITS_SCAN(METRIC_L2, true);
-    else VS_BITS_SCAN(METRIC_L2, false);
-#undef VS_BITS_SCAN
+    return a.self_mode == VS_SELF_KEEP && a.row0 == 0 && b.bits &&
+           (b.stride_words == 0 || b.stride_words >= (a.n_valid + 63) >> 6);
 }
 
 hipError_t launch_bits_scan(const RangeArgs& a, const BitsArgs& b, int G, int qy, const uint32_t* ids, int64_t m,
                             hipStream_t st) {
-    if (!bits_args_ok(a, b) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) || (!ids && m != 0))
-        return hipErrorInvalidValue;
-    if (a.dt == DT_F32) launch_bits_scan_dt<DT_F32>(a, b, G, qy, ids, m, st);
-    else if (a.dt == DT_BF16) launch_bits_scan_dt<DT_BF16>(a, b, G, qy, ids, m, st);
-    else if (a.dt == DT_F16) launch_bits_scan_dt<DT_F16>(a, b, G, qy, ids, m, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-template <int DT>
-static void launch_bits_refine_dt(const RangeArgs& a, const BitsArgs& b, const u64* glist, const int* gcnt, int lcap,
-                                  int ny, hipStream_t st) {
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = qbytes <= RS_QLDS_MAX;
-    const size_t lds = qlds ? qbytes : 0;
-    const dim3 grid(a.nq, ny), block(FS_THREADS);
-    const bool ip = a.metric == METRIC_IP;
-    const RsBitSink::Args sa{b.bits, b.stride_words};
-#define VS_BITS_REFINE(M, Q) hipLaunchKernelGGL((k_bits_refine<DT, M, Q>), grid, block, lds, st, a, glist, gcnt, lcap, sa)
-    if (ip && qlds) VS_BITS_REFINE(METRIC_IP, true);
-    else if (ip) VS_BITS_REFINE(METRIC_IP, false);
-    else if (qlds) VS_BITS_REFINE(METRIC_L2, true);
-    else VS_BITS_REFINE(METRIC_L2, false);
-#undef VS_BITS_REFINE
+    if (!bits_args_ok(a, b)) return hipErrorInvalidValue;
+    return rs_launch_scan<RsBitSink, false>(a, {b.bits, b.stride_words}, 0, 0, G, qy, ids, m, st);
 }
 
 hipError_t launch_bits_refine(const RangeArgs& a, const BitsArgs& b, const u64* glist, const int* gcnt, int lcap, int ny,
                               hipStream_t st) {
-    if (!bits_args_ok(a, b) || !glist || !gcnt || lcap <= 0 || ny < 1 || ny > 65535) return hipErrorInvalidValue;
-    if (a.dt == DT_BF16) launch_bits_refine_dt<DT_BF16>(a, b, glist, gcnt, lcap, ny, st);
-    else if (a.dt == DT_F16) launch_bits_refine_dt<DT_F16>(a, b, glist, gcnt, lcap, ny, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (!bits_args_ok(a, b)) return hipErrorInvalidValue;
+    return rs_launch_refine<RsBitSink, false>(a, {b.bits, b.stride_words}, glist, gcnt, lcap, ny, st);
 }
 
 // ---- bitmap kernels ---------------------------------------------------------------------------------

@@ -4,25 +4,16 @@
 // Queries are staged in blocks as the facet counts stage them; a block's answer is bits in a bitmap on the
 // device.  ANY: every query of every block sets bits in the one accumulator (zeroed once).  ALL: each query
 // of a block has a bitmap of its own (zeroed before the block), ANDed into the accumulator (preset to all
-// ones) after the block.  The SCREEN tier is the range search's (range_screen, then the refine with the bit
-// sink); a query whose survivor list a workgroup had to cut is re-answered by the scan over bits it keeps.
+// ones) after the block.  The tiers are the range search's (range_tiers, vs_range_tiers.h) with the bit sink.
 // The finish kernel applies negate, the members and the tail mask and counts; the ids are vs_sel_create's
 // compaction of the result.  Nothing grows with the number of passing rows.
-#include "vs_walk.h"
+#include "vs_range_tiers.h"
 
 using namespace vs;
 
 namespace {
 
-constexpr int kBitsScanRows = 64;  // rows per workgroup of the scan, at least (the range scan's figure)
-
 std::atomic<int64_t> g_scoresel_staging{64ll << 20};  // vs_set_scoresel_staging_bytes
-
-// the block's small device arrays and their host mirror
-struct BitsAuxH {
-    float radius[MFMA_QB];
-    int go[MFMA_QB];
-};
 
 struct BitsStats {
     int64_t m = 0, members = 0, tier = 0, rescanned = 0, blocks = 0;
@@ -110,72 +101,36 @@ void scoresel_run(vs_index* ix, const vs_sel* base, const float* q, const int64_
             ids_dev = c->row_ids.as<int64_t>();
             c->qdev.ensure((size_t)std::min<int64_t>(qb, nq) * ix->d * sizeof(float));
         }
-        c->rng_aux.ensure(sizeof(BitsAuxH));
-        uint8_t* ad = c->rng_aux.as<uint8_t>();
-        BitsAuxH h{};
-        // the sequence the scan's workgroups split, as range_block sizes it
-        const int64_t nseq = base ? base->m : n;
-        const int64_t ranges = (nseq + kBitsScanRows - 1) / kBitsScanRows;
-        const int G = (int)std::max<int64_t>(1, std::min<int64_t>(ix->num_cu, ranges));
+        c->rng_aux.ensure(sizeof(RangeAuxHead));
+        RangeAuxHead h{};
+        const int64_t nseq = base ? base->m : n;  // the sequence the scan's workgroups split
         for (int64_t q0 = 0; q0 < nq; q0 += qb) {
             const int nqb = (int)std::min<int64_t>(qb, nq - q0);
             ++stt.blocks;
             // (the previous block synchronised the stream after its copies from hq and h)
             if (ids) HIP_CHECK(launch_gather_rows(ix->dtype, ix->data, ids_dev + q0, nqb, ix->d, ix->dpad, c->qdev.as<float>(), st));
             else stage_queries(ix, c, q, q0, nqb, st);
-            for (int j = 0; j < nqb; ++j) {
-                h.radius[j] = radius[q0 + j];
-                h.go[j] = 1;
-            }
-            HIP_CHECK(hipMemcpyAsync(ad, &h, sizeof(h), hipMemcpyHostToDevice, st));
+            std::copy(radius + q0, radius + q0 + nqb, h.radius);
+            HIP_CHECK(hipMemcpyAsync(c->rng_aux.p, h.radius, sizeof(h.radius), hipMemcpyHostToDevice, st));
             if (all) HIP_CHECK(hipMemsetAsync(qbits.p, 0, (size_t)nqb * wbytes, st));
-            RangeArgs a{};
-            a.corpus = ix->data;
-            a.d = ix->d;
-            a.dpad = ix->dpad;
-            a.dt = ix->dtype;
-            a.metric = ix->metric;
+            RangeArgs a = range_index_args(ix);
             a.n_valid = n;
             a.q = c->qdev.as<float>();
             a.nq = nqb;
-            a.radius = (const float*)(ad + offsetof(BitsAuxH, radius));
-            a.go = (const int*)(ad + offsetof(BitsAuxH, go));
-            a.self_mode = VS_SELF_KEEP;
+            a.radius = range_aux_radius(c);
             const BitsArgs b{all ? qbits.as<unsigned long long>() : acc.as<unsigned long long>(), all ? nwords : 0};
-            bool scan = true;
             HIP_CHECK(hipEventRecord(e0, st));
-            if (range_mode != VS_RANGE_SCAN && range_screen_applies(ix, base, nqb)) {
-                const ScreenArgs s = range_screen(ix, c, a.q, nqb, a.radius, st);
-                RangeArgs r = a;
-                r.go = nullptr;
-                const int ny = std::max(1, std::min(32, 2 * ix->num_cu / nqb));
-                HIP_CHECK(launch_bits_refine(r, b, s.glist, s.gcnt, s.lcap, ny, st));
-                std::vector<u64> drop_h((size_t)nqb), thr_h((size_t)nqb);
-                HIP_CHECK(hipMemcpyAsync(drop_h.data(), s.drop, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipMemcpyAsync(thr_h.data(), s.thr0, sizeof(u64) * nqb, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                // a workgroup compacted the query's buffer and may have cut rows above the threshold: the list
-                // may be incomplete and the scan answers the query.  Unlike the facet counts' row of counters,
-                // its bits are NOT cleared: every bit the refine set belongs to a row that passes the exact
-                // predicate, the scan sets the rest, and setting a bit twice changes nothing.
-                scan = false;
-                for (int j = 0; j < nqb; ++j) {
-                    h.go[j] = drop_h[j] > thr_h[j] ? 1 : 0;
-                    if (h.go[j]) {
-                        scan = true;
-                        ++stt.rescanned;
-                    }
-                }
-                if (scan) HIP_CHECK(hipMemcpyAsync(ad, &h, sizeof(h), hipMemcpyHostToDevice, st));
-                stt.tier = VS_RANGE_SCREEN;
-            }
-            HIP_CHECK(hipEventRecord(e1, st));
-            if (scan) {
-                // a short sequence, or few workgroups per CU: deal the queries over slices of the grid
-                const int qy = std::max(1, std::min(nqb, 4 * ix->num_cu / G));
-                HIP_CHECK(launch_bits_scan(a, b, G, qy, base ? base->ids : nullptr, base ? base->m : 0, st));
-                if (stt.tier == 0) stt.tier = VS_RANGE_SCAN;
-            }
+            const RangeTiers t = range_tiers(
+                ix, c, a, h, nqb, base ? base->ids : nullptr, base ? base->m : 0, nseq, nullptr, base, range_mode, st, e1,
+                [&](const RangeArgs& r, const ScreenArgs& s, int ny) {
+                    HIP_CHECK(launch_bits_refine(r, b, s.glist, s.gcnt, s.lcap, ny, st));
+                },
+                [&](const RangeArgs& r, int G, int qy, const uint32_t* sids, int64_t m) {
+                    HIP_CHECK(launch_bits_scan(r, b, G, qy, sids, m, st));
+                });
+            if (t.screened) stt.tier = VS_RANGE_SCREEN;
+            else if (stt.tier == 0) stt.tier = VS_RANGE_SCAN;
+            stt.rescanned += t.rescanned;
             if (all) HIP_CHECK(launch_bits_fold(acc.as<uint64_t>(), qbits.as<uint64_t>(), nqb, nwords, st));
             HIP_CHECK(hipEventRecord(e2, st));
             HIP_CHECK(hipStreamSynchronize(st));

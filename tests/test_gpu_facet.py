@@ -312,8 +312,8 @@ def test_query_outside_lds(idx):
 # ---- the screen tier ---------------------------------------------------------------------------------------
 def test_screen_overflow_goes_to_the_scan(idx):
     """The construction of test_gpu_range.py: 4,000 copies of one vector stored contiguously and a radius
-    just below their score, so a workgroup of the screen compacts its list.  The query's counter row
-    starts again from zero and the scan answers it: no row counted twice, none lost."""
+    just below their score, so a workgroup of the screen compacts its list.  The scan answers the query
+    and the refine leaves it alone: no row counted twice, none lost."""
     rng = np.random.default_rng(19)
     N, d, nq = 300000, 64, 9
     x = rng.standard_normal((N, d)).astype(np.float32)
@@ -331,6 +331,35 @@ def test_screen_overflow_goes_to_the_scan(idx):
     for form in ("auto", "lds", "global"):
         for tier in ("screen", "auto"):
             assert stats[tier, form]["tier"] == "screen" and stats[tier, form]["rescanned"] >= 1, (tier, form)
+    groups.close()
+    ix.close()
+
+
+def test_screen_overflow_of_some_queries_of_a_block(idx):
+    """The construction above with 9 random queries in the same block, each with the radius of its 40th
+    best row: their lists are complete and the refine counts them, while the scan counts the 9 whose
+    list a workgroup cut -- one block, both tiers, every query through exactly one of them.  The commit
+    before the shared tier driver reported 9 re-answered queries under every tier and form, hence `== 9`."""
+    rng = np.random.default_rng(19)
+    N, d, nq = 300000, 64, 9
+    x = rng.standard_normal((N, d)).astype(np.float32)
+    v = x[100000].copy()
+    x[100000:104000] = v
+    xs = O.round_dtype(x, "bf16")
+    q = (v[None, :] * (1.0 + 0.01 * np.arange(nq))[:, None] + 0.01 * rng.standard_normal((nq, d))).astype(np.float32)
+    score = O.canon_scores(xs[100000:100001], q, "ip")[:, 0].astype(np.float32)
+    keys = _keys12(N, rng)
+    q2 = rng.standard_normal((nq, d)).astype(np.float32)
+    q = np.concatenate([q, q2])
+    radius = np.concatenate([np.nextafter(score, np.float32(-np.inf)), _kth_D(xs, q2, "ip", 40)])
+    ix = idx.FlatIndex(d, "ip", "bf16")
+    ix.add(x)
+    groups = ix.group_keys(keys)
+    (totals, _), stats = _check(ix, xs, q, radius, "ip", keys, groups)
+    assert (totals[:nq] >= 4000).all() and totals[nq:].tolist() == [39] * nq
+    for form in ("auto", "lds", "global"):
+        for tier in ("screen", "auto"):
+            assert stats[tier, form]["tier"] == "screen" and stats[tier, form]["rescanned"] == 9, (tier, form)
     groups.close()
     ix.close()
 

@@ -265,6 +265,31 @@ def test_screen_overflow_goes_to_the_scan(idx):
     ix.close()
 
 
+def test_screen_overflow_of_some_queries_of_a_block(idx):
+    """The construction above with 9 random queries in the same block, each with the radius of its 40th
+    best row: their lists are complete and the refine answers them, while the scan answers the 9 whose
+    list a workgroup cut -- one block, both tiers, every query through exactly one of them.  The commit
+    before the shared tier driver reported 9 re-answered queries under both modes, hence `== 9`."""
+    rng = np.random.default_rng(19)
+    N, d, nq = 300000, 64, 9
+    x = rng.standard_normal((N, d)).astype(np.float32)
+    v = x[100000].copy()
+    x[100000:104000] = v
+    xs = O.round_dtype(x, "bf16")
+    q = (v[None, :] * (1.0 + 0.01 * np.arange(nq))[:, None] + 0.01 * rng.standard_normal((nq, d))).astype(np.float32)
+    score = O.canon_scores(xs[100000:100001], q, "ip")[:, 0].astype(np.float32)
+    q2 = rng.standard_normal((nq, d)).astype(np.float32)
+    q = np.concatenate([q, q2])
+    radius = np.concatenate([np.nextafter(score, np.float32(-np.inf)), _kth_D(xs, q2, "ip", 40)])
+    ix = idx.FlatIndex(d, "ip", "bf16")
+    ix.add(x)
+    (lims, _, _), stats = _check(ix, xs, q, radius, "ip")
+    assert (np.diff(lims)[:nq] >= 4000).all() and np.diff(lims)[nq:].tolist() == [39] * nq
+    for mode in ("screen", "auto"):
+        assert stats[mode]["tier"] == "screen" and stats[mode]["rescanned"] == 9, mode
+    ix.close()
+
+
 # ---- consistency with top-k ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("metric,dtype,nq", [("ip", "f32", 3), ("l2", "bf16", 12), ("ip", "f16", 2)])
 def test_range_result_is_a_prefix_of_topk(idx, metric, dtype, nq):
