@@ -116,6 +116,19 @@ __device__ __forceinline__ void unpack16(const uint4 r, float* v) {
     }
 }
 
+// element e (a constant after unrolling) of a group's 8 values held as 16 B units: unpack16, one value
+template <int DT>
+__device__ __forceinline__ float unpack_elem(const uint4* r, int e) {
+    if constexpr (DT == DT_F32) {
+        const uint4 w = r[e >> 2];
+        return __uint_as_float((e & 3) == 0 ? w.x : (e & 3) == 1 ? w.y : (e & 3) == 2 ? w.z : w.w);
+    } else {
+        const uint32_t w = (e >> 1) == 0 ? r[0].x : (e >> 1) == 1 ? r[0].y : (e >> 1) == 2 ? r[0].z : r[0].w;
+        if constexpr (DT == DT_BF16) return __uint_as_float((e & 1) ? (w & 0xFFFF0000u) : (w << 16));
+        else return f16_bits_to_f32((e & 1) ? (w >> 16) : (w & 0xFFFFu));
+    }
+}
+
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -606,7 +619,10 @@ __device__ __forceinline__ void sort_valid_best_first(double* sc, uint32_t* ids,
 // order and accumulates them sequentially, then an xor-butterfly 32..1 -- the expression tree of the
 // oracle's orc_canon_scores (oracle/vs_oracle.c), so scores are bit-identical.  All R rows' gathers
 // are issued before any is consumed (R rows of d x es bytes in flight per wave); a row's piece of a
-// chunk is one 128 B line.
+// chunk is one 128 B line.  The loop is bound by instruction issue before it is bound by HBM, so a
+// full pass runs unguarded with the query values held in registers across the R rows and one fp64
+// FMA per element (inner product); only the remainder keeps its guards.  out[i] of an absent row
+// is 0.
 template <int DT>
 constexpr int refine_rows() { return DT == DT_F32 ? 2 : 4; }  // (fp32 rows: twice the registers)
 template <int DT, int METRIC, bool QLDS, int R>
@@ -618,31 +634,83 @@ __device__ __forceinline__ void exact_score_rows(const uint8_t* __restrict__ cor
     constexpr int NV = DT == DT_F32 ? 2 : 1;
     constexpr int RU = 3;
     constexpr int CE = CHB / ES;
+    // a lane's groups lie 64 groups = 512 elements = a whole number of chunks apart: from one group to the
+    // lane's next a row's pointer moves by the constant STEP (rb: the lane's current group g0 of each row)
+    constexpr int64_t STEP = (int64_t)(512 / CE) * TR * CHB;
     const uint8_t* rb[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         const int64_t r = row[i] >= 0 ? row[i] : row[0];
-        rb[i] = corpus + (r / TR) * (int64_t)TR * dpad * ES + (r % TR) * CHB;
+        rb[i] = corpus + (r / TR) * (int64_t)TR * dpad * ES + (r % TR) * CHB +
+                (int64_t)(8 * lane / CE) * TR * CHB + (8 * lane % CE) * ES;
     }
     const int ng = (d + 7) >> 3;
     double acc[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) acc[i] = 0.0;
-    for (int g0 = lane; g0 < ng; g0 += 64 * RU) {
+    int g0 = lane;
+    // Full passes: this lane's RU groups all exist and hold 8 elements each, so the body is straight-line
+    // code -- no element guard, no branch on a row being present (an absent row's loads go to row[0]'s
+    // address; its sum is dropped at the end) -- and each query value is read once for the R rows, one
+    // value live at a time (the refine kernels run 1024 threads: 128 VGPRs, 48 of them the rows in flight).
+    if ((d & 7) == 0)
+        for (; g0 + 64 * (RU - 1) < ng; g0 += 64 * RU) {
+            uint4 raw[RU][R][NV];
+#pragma unroll
+            for (int u = 0; u < RU; ++u)
+#pragma unroll
+                for (int i = 0; i < R; ++i)
+#pragma unroll
+                    for (int v = 0; v < NV; ++v) raw[u][i][v] = *(const uint4*)(rb[i] + u * STEP + 16 * v);
+#pragma unroll
+            for (int i = 0; i < R; ++i) rb[i] += RU * STEP;
+            const double* qp = qs + g0;  // (QLDS) group g0's 8 values: qp[e * ng]
+            const float* qgp = qg + 8 * g0;
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const double qq = QLDS ? qp[e * ng + 64 * u] : (double)qgp[512 * u + e];
+#pragma unroll
+                    for (int i = 0; i < R; ++i) {
+                        const double xa = (double)unpack_elem<DT>(raw[u][i], e);
+                        if constexpr (METRIC == METRIC_IP) {
+                            // x is a bf16 / f16 / f32 value and q an f32 value: x * q has at most
+                            // 24 + 24 significant bits and an exponent within [-298, 256], so it
+                            // is exact in fp64 (no rounding, overflow or underflow), and
+                            // fl(acc + fl(x * q)) = fl(acc + x * q) = fma(x, q, acc) bit for bit
+                            // for every finite input (a non-finite input gives a non-finite or
+                            // NaN score either way)
+                            acc[i] = __builtin_fma(xa, qq, acc[i]);
+                        } else {  // (x - q and its square do round: separate operations)
+                            const double da = xa - qq;
+                            const double pa = da * da;
+                            acc[i] = acc[i] + pa;
+                        }
+                    }
+                    // one element's work at a time (the scheduler otherwise hoists conversions and query
+                    // reads until the kernel spills; fp32 rows scored for L2 against a global-memory query
+                    // are the one shape it does better left alone)
+                    if constexpr (QLDS || DT != DT_F32 || METRIC != METRIC_L2) __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    // Remainder: a partial last pass, or d not a multiple of 8 -- every group and element guarded
+    for (; g0 < ng; g0 += 64 * RU) {
         uint4 raw[RU][R][NV];
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const int g = g0 + 64 * u;
             if (g < ng) {
-                const int e0 = 8 * g;
-                const int64_t off = (int64_t)(e0 / CE) * TR * CHB + (e0 % CE) * ES;
 #pragma unroll
                 for (int i = 0; i < R; ++i)
                     if (i == 0 || row[i] >= 0)
 #pragma unroll
-                        for (int v = 0; v < NV; ++v) raw[u][i][v] = *(const uint4*)(rb[i] + off + 16 * v);
+                        for (int v = 0; v < NV; ++v) raw[u][i][v] = *(const uint4*)(rb[i] + u * STEP + 16 * v);
             }
         }
+#pragma unroll
+        for (int i = 0; i < R; ++i) rb[i] += RU * STEP;
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const int g = g0 + 64 * u;
@@ -681,7 +749,7 @@ __device__ __forceinline__ void exact_score_rows(const uint8_t* __restrict__ cor
             acc[i] = acc[i] + o;
         }
 #pragma unroll
-    for (int i = 0; i < R; ++i) out[i] = acc[i];
+    for (int i = 0; i < R; ++i) out[i] = (i == 0 || row[i] >= 0) ? acc[i] : 0.0;  // (absent: 0, as ever)
 }
 
 }  // namespace vs

@@ -38,7 +38,7 @@ def build():
         ("    nA = min(nA, RFW_CAP);\n    __syncthreads();\n", 3, "after"),
         ("    rfw_score<DT, METRIC, QLDS>(a, ids, sc, 0, nA, qs, qv);\n    __syncthreads();\n", 4, "after"),
         ("    sort_valid_best_first<METRIC_IP>(sc, ids, nA, nA2);  // phase A best first", 5, "after_line"),
-        ("            a.pa_tA[q] = tA;\n        }\n", 11, "after_sync"),
+        ("            if (a.rows) atomicAdd(a.rows, (unsigned long long)nA);\n        }\n", 11, "after_sync"),
         ("    const bool overflow = nA2 + nB > RFW_CAP;\n", 6, "before_sync"),
         ("    rfw_score<DT, METRIC, QLDS>(a, ids, sc, nA2, nA2 + nB, qs, qv);\n    __syncthreads();\n", 7, "after"),
         ("    const int nF = nA + nb_s;\n", 8, "before"),
