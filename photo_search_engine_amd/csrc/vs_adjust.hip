@@ -47,48 +47,14 @@ __global__ void __launch_bounds__(FS_THREADS) k_adjust_scan(FullScanArgs a, int 
     fs_scan_body<DT, METRIC, QLDS, SEL, AdjustXf>(a, KL, ids, m, AdjustXf{r});
 }
 
-template <int DT, int METRIC, bool QLDS, bool SEL>
-static void launch_adjust_scan_one(const FullScanArgs& a, int KL, size_t lds, const AdjustRows& r, const uint32_t* ids,
-                                   int64_t m, int qy, hipStream_t st) {
-    set_lds_attr((const void*)k_adjust_scan<DT, METRIC, QLDS, SEL>, 152 * 1024);
-    hipLaunchKernelGGL((k_adjust_scan<DT, METRIC, QLDS, SEL>), dim3(a.G, SEL ? qy : 1), dim3(FS_THREADS), lds, st, a, KL, r,
-                       ids, m);
-}
-
-template <int DT, int METRIC>
-static void launch_adjust_scan_m(const FullScanArgs& a, int KL, size_t lds, bool qlds, const AdjustRows& r,
-                                 const uint32_t* ids, int64_t m, int qy, hipStream_t st) {
-    if (ids) {
-        if (qlds) launch_adjust_scan_one<DT, METRIC, true, true>(a, KL, lds, r, ids, m, qy, st);
-        else launch_adjust_scan_one<DT, METRIC, false, true>(a, KL, lds, r, ids, m, qy, st);
-    } else {
-        if (qlds) launch_adjust_scan_one<DT, METRIC, true, false>(a, KL, lds, r, ids, m, qy, st);
-        else launch_adjust_scan_one<DT, METRIC, false, false>(a, KL, lds, r, ids, m, qy, st);
-    }
-}
-
-template <int DT>
-static void launch_adjust_scan_dt(const FullScanArgs& a, int KL, size_t lds, bool qlds, const AdjustRows& r,
-                                  const uint32_t* ids, int64_t m, int qy, hipStream_t st) {
-    if (a.metric == METRIC_IP) launch_adjust_scan_m<DT, METRIC_IP>(a, KL, lds, qlds, r, ids, m, qy, st);
-    else launch_adjust_scan_m<DT, METRIC_L2>(a, KL, lds, qlds, r, ids, m, qy, st);
-}
-
 hipError_t launch_adjust_scan(const FullScanArgs& a, const AdjustRows& r, const uint32_t* ids, int64_t m, int qy,
                               hipStream_t st) {
-    if (qy < 1 || qy > a.nq || qy > 65535) return hipErrorInvalidValue;
-    if (a.nq <= 0 || a.k <= 0 || a.k > KP_MAX || a.G <= 0 || a.G > FS_B || a.n_valid <= 0 || !a.cert || !a.I || !a.gsc ||
-        !a.gid || !a.gdone || !a.q || !a.corpus || !r.scale || !r.bias || r.n_cov <= 0 || (!ids && a.n_valid != r.n_cov) ||
-        (ids && m <= 0) || (a.metric != METRIC_IP && a.metric != METRIC_L2))
+    if (qy < 1 || qy > a.nq || qy > 65535 || !r.scale || !r.bias || r.n_cov <= 0 || (!ids && a.n_valid != r.n_cov) ||
+        (ids && m <= 0))
         return hipErrorInvalidValue;
-    int KL;
-    bool qlds;
-    const size_t lds = fs_lds_bytes(a.k, a.d, &KL, &qlds);
-    if (a.dt == DT_F32) launch_adjust_scan_dt<DT_F32>(a, KL, lds, qlds, r, ids, m, qy, st);
-    else if (a.dt == DT_BF16) launch_adjust_scan_dt<DT_BF16>(a, KL, lds, qlds, r, ids, m, qy, st);
-    else if (a.dt == DT_F16) launch_adjust_scan_dt<DT_F16>(a, KL, lds, qlds, r, ids, m, qy, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return fs_launch_scan(
+        a, 1, ids != nullptr, ids ? qy : 1, st,
+        [](auto dt, auto metric, auto qlds, auto sel) { return k_adjust_scan<dt, metric, qlds, sel>; }, r, ids, m);
 }
 
 // ---- the walk ------------------------------------------------------------------------------------
@@ -210,22 +176,7 @@ __global__ void __launch_bounds__(AJ_THREADS) k_adjust_walk(AdjustWalkArgs a, in
     }
 }
 
-size_t adjust_walk_lds(int64_t n_entries, int d) {
-    size_t n2 = 64;
-    while ((int64_t)n2 < n_entries) n2 <<= 1;
-    return n2 * 12 + (size_t)((d + 7) >> 3) * 64;
-}
-
-template <int DT>
-static void launch_adjust_walk_dt(const AdjustWalkArgs& a, int nq, int n2, size_t lds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        set_lds_attr((const void*)k_adjust_walk<DT, METRIC_IP>, (int)AJ_DYN_CAP);
-        hipLaunchKernelGGL((k_adjust_walk<DT, METRIC_IP>), dim3(nq), dim3(AJ_THREADS), lds, st, a, n2);
-    } else {
-        set_lds_attr((const void*)k_adjust_walk<DT, METRIC_L2>, (int)AJ_DYN_CAP);
-        hipLaunchKernelGGL((k_adjust_walk<DT, METRIC_L2>), dim3(nq), dim3(AJ_THREADS), lds, st, a, n2);
-    }
-}
+size_t adjust_walk_lds(int64_t n_entries, int d) { return pow2_at_least(n_entries, 64) * 12 + query_lds_bytes(d); }
 
 hipError_t launch_adjust_walk(const AdjustWalkArgs& a, int nq, hipStream_t st) {
     if (nq <= 0) return hipSuccess;
@@ -238,13 +189,11 @@ hipError_t launch_adjust_walk(const AdjustWalkArgs& a, int nq, hipStream_t st) {
         return hipErrorInvalidValue;
     const size_t lds = adjust_walk_lds(n, a.d);
     if (lds > AJ_DYN_CAP) return hipErrorInvalidValue;
-    int n2 = 64;
-    while (n2 < n) n2 <<= 1;
-    if (a.dt == DT_F32) launch_adjust_walk_dt<DT_F32>(a, nq, n2, lds, st);
-    else if (a.dt == DT_BF16) launch_adjust_walk_dt<DT_BF16>(a, nq, n2, lds, st);
-    else if (a.dt == DT_F16) launch_adjust_walk_dt<DT_F16>(a, nq, n2, lds, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const int n2 = (int)pow2_at_least(n, 64);
+    const bool known = dispatch(a.dt, a.metric, [&](auto dt, auto metric) {
+        launch_kernel(k_adjust_walk<dt, metric>, (int)AJ_DYN_CAP, dim3(nq), dim3(AJ_THREADS), lds, st, a, n2);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vs

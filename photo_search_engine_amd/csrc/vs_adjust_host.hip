@@ -171,7 +171,7 @@ struct AjCall {
         for (int64_t q0 = 0; q0 < m; q0 += MFMA_QB) {
             const int nqb = (int)std::min<int64_t>(MFMA_QB, m - q0);
             const SearchOut out{nullptr, scanI.as<int64_t>() + q0 * ks, nullptr, cert.as<int>() + q0};
-            FullScanArgs a = full_scan_args(ix, c, ids ? n_ids : aj->n_cov, kAdjScanRows, std::min(ix->num_cu, 512 /* FS_B */),
+            FullScanArgs a = full_scan_args(ix, c, ids ? n_ids : aj->n_cov, kAdjScanRows, std::min(ix->num_cu, FS_B),
                                             qd + q0 * ix->d, nqb, ks, out, true, st);
             if (!ids) a.n_valid = aj->n_cov;
             // a short list leaves CUs idle: deal the block's queries over as many slices as fill them

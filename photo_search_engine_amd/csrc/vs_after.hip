@@ -49,29 +49,21 @@ __global__ void __launch_bounds__(64) k_after_score(const uint8_t* __restrict__ 
     if (lane == 0) key[qi] = METRIC == METRIC_L2 ? -s[0] : s[0];
 }
 
-template <int DT>
-static void launch_after_score_dt(int metric, const uint8_t* corpus, int d, int dpad, int64_t n_valid, const float* q,
-                                  const int64_t* after, int nq, double* key, hipStream_t st) {
-    if (metric == METRIC_IP)
-        hipLaunchKernelGGL((k_after_score<DT, METRIC_IP>), dim3(nq), dim3(64), 0, st, corpus, d, dpad, n_valid, q, after, key);
-    else
-        hipLaunchKernelGGL((k_after_score<DT, METRIC_L2>), dim3(nq), dim3(64), 0, st, corpus, d, dpad, n_valid, q, after, key);
-}
-
 hipError_t launch_after_score(int dt, int metric, const uint8_t* corpus, int d, int dpad, int64_t n_valid, const float* q,
                               const int64_t* after, int64_t nq, double* key, hipStream_t st) {
     if (nq <= 0) return hipSuccess;
     if (!corpus || !q || !after || !key || d < 1 || n_valid < 0 || (metric != METRIC_IP && metric != METRIC_L2))
         return hipErrorInvalidValue;
     const int64_t qmax = 65536;  // workgroups of one launch
-    for (int64_t q0 = 0; q0 < nq; q0 += qmax) {
+    bool known = true;
+    for (int64_t q0 = 0; q0 < nq && known; q0 += qmax) {
         const int n = (int)std::min(qmax, nq - q0);
-        if (dt == DT_F32) launch_after_score_dt<DT_F32>(metric, corpus, d, dpad, n_valid, q + q0 * d, after + q0, n, key + q0, st);
-        else if (dt == DT_BF16) launch_after_score_dt<DT_BF16>(metric, corpus, d, dpad, n_valid, q + q0 * d, after + q0, n, key + q0, st);
-        else if (dt == DT_F16) launch_after_score_dt<DT_F16>(metric, corpus, d, dpad, n_valid, q + q0 * d, after + q0, n, key + q0, st);
-        else return hipErrorInvalidValue;
+        known = dispatch(dt, metric, [&](auto dt_c, auto metric_c) {
+            launch_kernel(k_after_score<dt_c, metric_c>, 0, dim3(n), dim3(64), 0, st, corpus, d, dpad, n_valid, q + q0 * d,
+                          after + q0, key + q0);
+        });
     }
-    return hipGetLastError();
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ---- the cut -------------------------------------------------------------------------------------
@@ -162,31 +154,17 @@ __global__ void __launch_bounds__(AF_THREADS) k_after_cut(AfterCutArgs a) {
     }
 }
 
-static size_t after_cut_lds(int d) { return (size_t)((d + 7) >> 3) * 64; }
-
-template <int DT>
-static void launch_after_cut_dt(const AfterCutArgs& a, int nq, size_t lds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        set_lds_attr((const void*)k_after_cut<DT, METRIC_IP>, (int)after_cut_lds(AF_D_MAX));
-        hipLaunchKernelGGL((k_after_cut<DT, METRIC_IP>), dim3(nq), dim3(AF_THREADS), lds, st, a);
-    } else {
-        set_lds_attr((const void*)k_after_cut<DT, METRIC_L2>, (int)after_cut_lds(AF_D_MAX));
-        hipLaunchKernelGGL((k_after_cut<DT, METRIC_L2>), dim3(nq), dim3(AF_THREADS), lds, st, a);
-    }
-}
-
 hipError_t launch_after_cut(const AfterCutArgs& a, int nq, hipStream_t st) {
     if (nq <= 0) return hipSuccess;
     if (nq > 65536 || a.k < 1 || a.k > K_MAX || a.L < 1 || a.L > K_MAX || a.d < 1 || a.d > AF_D_MAX || !a.corpus || !a.q ||
         !a.I_list || !a.D_list || a.n_valid < 1 || a.n_valid > 0xFFFFFFFFll || !a.cur.id || !a.cur.key || !a.I || !a.D ||
         !a.rank || !a.complete || (a.metric != METRIC_IP && a.metric != METRIC_L2))
         return hipErrorInvalidValue;
-    const size_t lds = after_cut_lds(a.d);
-    if (a.dt == DT_F32) launch_after_cut_dt<DT_F32>(a, nq, lds, st);
-    else if (a.dt == DT_BF16) launch_after_cut_dt<DT_BF16>(a, nq, lds, st);
-    else if (a.dt == DT_F16) launch_after_cut_dt<DT_F16>(a, nq, lds, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const bool known = dispatch(a.dt, a.metric, [&](auto dt, auto metric) {
+        launch_kernel(k_after_cut<dt, metric>, (int)query_lds_bytes(AF_D_MAX), dim3(nq), dim3(AF_THREADS),
+                      query_lds_bytes(a.d), st, a);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ---- the scan ------------------------------------------------------------------------------------
@@ -214,48 +192,14 @@ __global__ void __launch_bounds__(FS_THREADS) k_after_scan(FullScanArgs a, int K
     fs_scan_body<DT, METRIC, QLDS, SEL, AfterXf>(a, KL, ids, m, AfterXf{cur, rank});
 }
 
-template <int DT, int METRIC, bool QLDS, bool SEL>
-static void launch_after_scan_one(const FullScanArgs& a, int KL, size_t lds, const AfterCursor& cur, unsigned long long* rank,
-                                  const uint32_t* ids, int64_t m, int qy, hipStream_t st) {
-    set_lds_attr((const void*)k_after_scan<DT, METRIC, QLDS, SEL>, 152 * 1024);
-    hipLaunchKernelGGL((k_after_scan<DT, METRIC, QLDS, SEL>), dim3(a.G, SEL ? qy : 1), dim3(FS_THREADS), lds, st, a, KL, cur,
-                       rank, ids, m);
-}
-
-template <int DT, int METRIC>
-static void launch_after_scan_m(const FullScanArgs& a, int KL, size_t lds, bool qlds, const AfterCursor& cur,
-                                unsigned long long* rank, const uint32_t* ids, int64_t m, int qy, hipStream_t st) {
-    if (ids) {
-        if (qlds) launch_after_scan_one<DT, METRIC, true, true>(a, KL, lds, cur, rank, ids, m, qy, st);
-        else launch_after_scan_one<DT, METRIC, false, true>(a, KL, lds, cur, rank, ids, m, qy, st);
-    } else {
-        if (qlds) launch_after_scan_one<DT, METRIC, true, false>(a, KL, lds, cur, rank, ids, m, qy, st);
-        else launch_after_scan_one<DT, METRIC, false, false>(a, KL, lds, cur, rank, ids, m, qy, st);
-    }
-}
-
-template <int DT>
-static void launch_after_scan_dt(const FullScanArgs& a, int KL, size_t lds, bool qlds, const AfterCursor& cur,
-                                 unsigned long long* rank, const uint32_t* ids, int64_t m, int qy, hipStream_t st) {
-    if (a.metric == METRIC_IP) launch_after_scan_m<DT, METRIC_IP>(a, KL, lds, qlds, cur, rank, ids, m, qy, st);
-    else launch_after_scan_m<DT, METRIC_L2>(a, KL, lds, qlds, cur, rank, ids, m, qy, st);
-}
-
 hipError_t launch_after_scan(const FullScanArgs& a, const AfterCursor& cur, unsigned long long* rank, const uint32_t* ids,
                              int64_t m, int qy, hipStream_t st) {
-    if (qy < 1 || qy > a.nq || qy > 65535) return hipErrorInvalidValue;
-    if (a.nq <= 0 || a.k <= 0 || a.k > KP_MAX || a.G <= 0 || a.G > FS_B || a.n_valid <= 0 || a.n_valid > 0xFFFFFFFFll ||
-        !a.cert || !a.I || !a.gsc || !a.gid || !a.gdone || !a.q || !a.corpus || a.gate || !a.all_queries || !cur.id ||
-        !cur.key || !rank || (ids && m <= 0) || (a.metric != METRIC_IP && a.metric != METRIC_L2))
+    if (qy < 1 || qy > a.nq || qy > 65535 || a.n_valid > 0xFFFFFFFFll || a.gate || !a.all_queries || !cur.id || !cur.key ||
+        !rank || (ids && m <= 0))
         return hipErrorInvalidValue;
-    int KL;
-    bool qlds;
-    const size_t lds = fs_lds_bytes(a.k, a.d, &KL, &qlds);
-    if (a.dt == DT_F32) launch_after_scan_dt<DT_F32>(a, KL, lds, qlds, cur, rank, ids, m, qy, st);
-    else if (a.dt == DT_BF16) launch_after_scan_dt<DT_BF16>(a, KL, lds, qlds, cur, rank, ids, m, qy, st);
-    else if (a.dt == DT_F16) launch_after_scan_dt<DT_F16>(a, KL, lds, qlds, cur, rank, ids, m, qy, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return fs_launch_scan(
+        a, 1, ids != nullptr, ids ? qy : 1, st,
+        [](auto dt, auto metric, auto qlds, auto sel) { return k_after_scan<dt, metric, qlds, sel>; }, cur, rank, ids, m);
 }
 
 }  // namespace vs

@@ -127,7 +127,7 @@ struct AfCall {
             const int nqb = (int)std::min<int64_t>(MFMA_QB, np - q0);
             const SearchOut out{scanD.as<float>() + q0 * ks, scanI.as<int64_t>() + q0 * ks, nullptr, cert.as<int>() + q0};
             const FullScanArgs a = full_scan_args(ix, c, ids ? n_ids : ix->ntotal, kAfterScanRows,
-                                                  std::min(ix->num_cu, 512 /* FS_B */), scanq.as<float>() + q0 * ix->d, nqb, ks,
+                                                  std::min(ix->num_cu, FS_B), scanq.as<float>() + q0 * ix->d, nqb, ks,
                                                   out, true, st);
             // a short list leaves CUs idle: deal the block's queries over as many slices as fill them
             const int qy = ids ? std::max(1, std::min(nqb, ix->num_cu / a.G)) : 1;

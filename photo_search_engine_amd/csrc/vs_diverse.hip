@@ -18,6 +18,7 @@
 // Every store is bounded: the outputs by k entries of the query's rows, the LDS arrays by nk < k <=
 // DV_K_MAX, by DV_BLOCK and by a.nqs slots of ng * 8 doubles.  Plain vector stores only.
 #include "vs_device.h"
+#include "vs_dispatch.h"
 
 namespace vs {
 
@@ -184,20 +185,8 @@ __global__ void __launch_bounds__(DV_THREADS) k_diverse_walk(DiverseArgs a) {
     }
 }
 
-template <int DT>
-static void launch_walk_dt(const DiverseArgs& a, int nq, size_t lds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        set_lds_attr((const void*)k_diverse_walk<DT, METRIC_IP>, (int)DV_DYN_CAP);
-        hipLaunchKernelGGL((k_diverse_walk<DT, METRIC_IP>), dim3(nq), dim3(DV_THREADS), lds, st, a);
-    } else {
-        set_lds_attr((const void*)k_diverse_walk<DT, METRIC_L2>, (int)DV_DYN_CAP);
-        hipLaunchKernelGGL((k_diverse_walk<DT, METRIC_L2>), dim3(nq), dim3(DV_THREADS), lds, st, a);
-    }
-}
-
 int diverse_query_slots(int d) {
-    const size_t slot = (size_t)((d + 7) >> 3) * 64;  // 8 * ng doubles
-    return (int)std::min<size_t>(DV_NW, DV_DYN_CAP / slot);
+    return (int)std::min<size_t>(DV_NW, DV_DYN_CAP / query_lds_bytes(d));
 }
 
 hipError_t launch_diverse_walk(const DiverseArgs& a, int nq, hipStream_t st) {
@@ -206,12 +195,11 @@ hipError_t launch_diverse_walk(const DiverseArgs& a, int nq, hipStream_t st) {
         !a.radius || !a.I || !a.D || !a.hidden || !a.nacc || !a.examined ||
         (a.metric != METRIC_IP && a.metric != METRIC_L2) || a.nqs < 1 || a.nqs != diverse_query_slots(a.d))
         return hipErrorInvalidValue;
-    const size_t lds = (size_t)a.nqs * ((a.d + 7) >> 3) * 64;
-    if (a.dt == DT_F32) launch_walk_dt<DT_F32>(a, nq, lds, st);
-    else if (a.dt == DT_BF16) launch_walk_dt<DT_BF16>(a, nq, lds, st);
-    else if (a.dt == DT_F16) launch_walk_dt<DT_F16>(a, nq, lds, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const size_t lds = (size_t)a.nqs * query_lds_bytes(a.d);
+    const bool known = dispatch(a.dt, a.metric, [&](auto dt, auto metric) {
+        launch_kernel(k_diverse_walk<dt, metric>, (int)DV_DYN_CAP, dim3(nq), dim3(DV_THREADS), lds, st, a);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vs

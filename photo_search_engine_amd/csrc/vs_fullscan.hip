@@ -30,37 +30,11 @@ __global__ void __launch_bounds__(FS_THREADS) k_full_scan(FullScanArgs a, int KL
     fs_scan_body<DT, METRIC, QLDS, false>(a, KL, nullptr, 0);
 }
 
-template <int DT, int METRIC, bool QLDS>
-static void launch_full_scan_one(const FullScanArgs& a, int KL, size_t lds, hipStream_t st) {
-    set_lds_attr((const void*)k_full_scan<DT, METRIC, QLDS>, 152 * 1024);
-    hipLaunchKernelGGL((k_full_scan<DT, METRIC, QLDS>), dim3(a.G), dim3(FS_THREADS), lds, st, a, KL);
-}
-
-template <int DT>
-static void launch_full_scan_dt(const FullScanArgs& a, int KL, size_t lds, bool qlds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        if (qlds) launch_full_scan_one<DT, METRIC_IP, true>(a, KL, lds, st);
-        else launch_full_scan_one<DT, METRIC_IP, false>(a, KL, lds, st);
-    } else {
-        if (qlds) launch_full_scan_one<DT, METRIC_L2, true>(a, KL, lds, st);
-        else launch_full_scan_one<DT, METRIC_L2, false>(a, KL, lds, st);
-    }
-}
-
 size_t full_scan_scratch_bytes(int nq, int G, int k) { return (size_t)nq * G * k * 12; }
 
 hipError_t launch_full_scan(const FullScanArgs& a, hipStream_t st) {
-    if (a.nq <= 0 || a.k <= 0 || a.k > KP_MAX || a.G <= 0 || a.G > FS_B || a.n_valid <= 0 || !a.cert || !a.I || !a.gsc || !a.gid ||
-        !a.gdone || !a.q || !a.corpus)
-        return hipErrorInvalidValue;
-    int KL;
-    bool qlds;
-    const size_t lds = fs_lds_bytes(a.k, a.d, &KL, &qlds);
-    if (a.dt == DT_F32) launch_full_scan_dt<DT_F32>(a, KL, lds, qlds, st);
-    else if (a.dt == DT_BF16) launch_full_scan_dt<DT_BF16>(a, KL, lds, qlds, st);
-    else if (a.dt == DT_F16) launch_full_scan_dt<DT_F16>(a, KL, lds, qlds, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return fs_launch_scan(a, 1, false, 1, st,
+                          [](auto dt, auto metric, auto qlds, auto) { return k_full_scan<dt, metric, qlds>; });
 }
 
 }  // namespace vs

@@ -38,18 +38,6 @@ __device__ __forceinline__ void fuse_pick(int mode, int j, double kj, double& f,
 }
 
 // ---- the scan ------------------------------------------------------------------------------------
-// dynamic LDS of one scan workgroup: fs_lds_bytes with m sub-queries in the query's place
-static size_t fuse_scan_lds(int k, int d, int m, int* KL_out, bool* qlds_out) {
-    int KL = 64;
-    while (KL < k) KL <<= 1;
-    const size_t base = (size_t)KL * 24 + (size_t)FS_B * 12;
-    const size_t qbytes = (size_t)m * ((d + 7) >> 3) * 64;
-    const bool qlds = base + qbytes <= 148 * 1024;
-    *KL_out = KL;
-    *qlds_out = qlds;
-    return qlds ? base + qbytes : base;
-}
-
 // fs_scan_body's fused transform: m sub-queries per query, the row's F (in the metric's own direction) to
 // the running top-k
 struct FuseXf {
@@ -86,49 +74,14 @@ __global__ void __launch_bounds__(FS_THREADS) k_fuse_scan(FullScanArgs a, int KL
     fs_scan_body<DT, METRIC, QLDS, SEL, FuseXf>(a, KL, sel_ids, sel_m, FuseXf{m, mode});
 }
 
-template <int DT, int METRIC, bool QLDS, bool SEL>
-static void launch_fuse_scan_one(const FullScanArgs& a, int KL, size_t lds, int m, int mode, const uint32_t* ids,
-                                 int64_t n_ids, int qy, hipStream_t st) {
-    set_lds_attr((const void*)k_fuse_scan<DT, METRIC, QLDS, SEL>, 152 * 1024);
-    hipLaunchKernelGGL((k_fuse_scan<DT, METRIC, QLDS, SEL>), dim3(a.G, qy), dim3(FS_THREADS), lds, st, a, KL, m,
-                       mode, ids, n_ids);
-}
-
-template <int DT, int METRIC>
-static void launch_fuse_scan_m(const FullScanArgs& a, int KL, size_t lds, bool qlds, int m, int mode, const uint32_t* ids,
-                               int64_t n_ids, int qy, hipStream_t st) {
-    if (ids) {
-        if (qlds) launch_fuse_scan_one<DT, METRIC, true, true>(a, KL, lds, m, mode, ids, n_ids, qy, st);
-        else launch_fuse_scan_one<DT, METRIC, false, true>(a, KL, lds, m, mode, ids, n_ids, qy, st);
-    } else {
-        if (qlds) launch_fuse_scan_one<DT, METRIC, true, false>(a, KL, lds, m, mode, ids, n_ids, qy, st);
-        else launch_fuse_scan_one<DT, METRIC, false, false>(a, KL, lds, m, mode, ids, n_ids, qy, st);
-    }
-}
-
-template <int DT>
-static void launch_fuse_scan_dt(const FullScanArgs& a, int KL, size_t lds, bool qlds, int m, int mode, const uint32_t* ids,
-                                int64_t n_ids, int qy, hipStream_t st) {
-    if (a.metric == METRIC_IP) launch_fuse_scan_m<DT, METRIC_IP>(a, KL, lds, qlds, m, mode, ids, n_ids, qy, st);
-    else launch_fuse_scan_m<DT, METRIC_L2>(a, KL, lds, qlds, m, mode, ids, n_ids, qy, st);
-}
-
 hipError_t launch_fuse_scan(const FullScanArgs& a, int m, int mode, const uint32_t* ids, int64_t n_ids, int qy,
                             hipStream_t st) {
-    if (qy < 1 || qy > a.nq || qy > 65535) return hipErrorInvalidValue;
-    if (m < 1 || m > FUSE_MAX_Q || (mode != FUSE_ANY && mode != FUSE_ALL) || a.nq <= 0 || a.k <= 0 || a.k > KP_MAX ||
-        a.G <= 0 || a.G > FS_B || a.n_valid <= 0 || a.n_valid > 0xFFFFFFFFll || !a.cert || !a.I || !a.gsc || !a.gid ||
-        !a.gdone || !a.q || !a.corpus || a.gate || !a.all_queries || (ids && n_ids <= 0) ||
-        (a.metric != METRIC_IP && a.metric != METRIC_L2))
+    if (qy < 1 || qy > a.nq || qy > 65535 || m < 1 || m > FUSE_MAX_Q || (mode != FUSE_ANY && mode != FUSE_ALL) ||
+        a.n_valid > 0xFFFFFFFFll || a.gate || !a.all_queries || (ids && n_ids <= 0))
         return hipErrorInvalidValue;
-    int KL;
-    bool qlds;
-    const size_t lds = fuse_scan_lds(a.k, a.d, m, &KL, &qlds);
-    if (a.dt == DT_F32) launch_fuse_scan_dt<DT_F32>(a, KL, lds, qlds, m, mode, ids, n_ids, qy, st);
-    else if (a.dt == DT_BF16) launch_fuse_scan_dt<DT_BF16>(a, KL, lds, qlds, m, mode, ids, n_ids, qy, st);
-    else if (a.dt == DT_F16) launch_fuse_scan_dt<DT_F16>(a, KL, lds, qlds, m, mode, ids, n_ids, qy, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return fs_launch_scan(
+        a, m, ids != nullptr, qy, st,
+        [](auto dt, auto metric, auto qlds, auto sel) { return k_fuse_scan<dt, metric, qlds, sel>; }, m, mode, ids, n_ids);
 }
 
 // ---- the walk ------------------------------------------------------------------------------------
@@ -298,22 +251,7 @@ __global__ void __launch_bounds__(FU_THREADS) k_fuse_walk(FuseWalkArgs a, int n2
     }
 }
 
-size_t fuse_walk_lds(int64_t n_entries, int d) {
-    size_t n2 = 64;
-    while ((int64_t)n2 < n_entries) n2 <<= 1;
-    return n2 * 12 + (size_t)((d + 7) >> 3) * 64;
-}
-
-template <int DT>
-static void launch_fuse_walk_dt(const FuseWalkArgs& a, int nq, int n2, size_t lds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        set_lds_attr((const void*)k_fuse_walk<DT, METRIC_IP>, (int)FUSE_DYN_CAP);
-        hipLaunchKernelGGL((k_fuse_walk<DT, METRIC_IP>), dim3(nq), dim3(FU_THREADS), lds, st, a, n2);
-    } else {
-        set_lds_attr((const void*)k_fuse_walk<DT, METRIC_L2>, (int)FUSE_DYN_CAP);
-        hipLaunchKernelGGL((k_fuse_walk<DT, METRIC_L2>), dim3(nq), dim3(FU_THREADS), lds, st, a, n2);
-    }
-}
+size_t fuse_walk_lds(int64_t n_entries, int d) { return pow2_at_least(n_entries, 64) * 12 + query_lds_bytes(d); }
 
 hipError_t launch_fuse_walk(const FuseWalkArgs& a, int nq, hipStream_t st) {
     if (nq <= 0) return hipSuccess;
@@ -325,13 +263,11 @@ hipError_t launch_fuse_walk(const FuseWalkArgs& a, int nq, hipStream_t st) {
         return hipErrorInvalidValue;
     const size_t lds = fuse_walk_lds(n, a.d);
     if (lds > FUSE_DYN_CAP) return hipErrorInvalidValue;
-    int n2 = 64;
-    while (n2 < n) n2 <<= 1;
-    if (a.dt == DT_F32) launch_fuse_walk_dt<DT_F32>(a, nq, n2, lds, st);
-    else if (a.dt == DT_BF16) launch_fuse_walk_dt<DT_BF16>(a, nq, n2, lds, st);
-    else if (a.dt == DT_F16) launch_fuse_walk_dt<DT_F16>(a, nq, n2, lds, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const int n2 = (int)pow2_at_least(n, 64);
+    const bool known = dispatch(a.dt, a.metric, [&](auto dt, auto metric) {
+        launch_kernel(k_fuse_walk<dt, metric>, (int)FUSE_DYN_CAP, dim3(nq), dim3(FU_THREADS), lds, st, a, n2);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vs

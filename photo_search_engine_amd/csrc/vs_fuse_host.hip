@@ -111,7 +111,7 @@ struct FuCall {
             const int nqb = (int)std::min<int64_t>(MFMA_QB, n - q0);
             const SearchOut out{nullptr, scanI.as<int64_t>() + q0 * ks, nullptr, cert.as<int>() + q0};
             const FullScanArgs a = full_scan_args(ix, c, ids ? n_ids : ix->ntotal, kFuseScanRows,
-                                                  std::min(ix->num_cu, 512 /* FS_B */), qd + q0 * m * ix->d, nqb, ks, out,
+                                                  std::min(ix->num_cu, FS_B), qd + q0 * m * ix->d, nqb, ks, out,
                                                   true, st);
             // fewer workgroups than CUs (a short list, or deep lists under the scratch budget): deal the block's
             // queries over as many slices as fill them

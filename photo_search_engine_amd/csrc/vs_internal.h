@@ -53,6 +53,16 @@ inline int pad_dim(int d, int dt) {
 inline int64_t tile_bytes(int dpad, int dt) { return (int64_t)TR * dpad * es_of(dt); }
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
+// the query as fp64 in LDS: (d + 7) / 8 groups of 8 elements
+__host__ __device__ inline size_t query_lds_bytes(int d) { return (size_t)((d + 7) >> 3) * 64; }
+
+// the least floor * 2^i that is >= n (floor: a power of two)
+inline int64_t pow2_at_least(int64_t n, int64_t floor) {
+    int64_t p = floor;
+    while (p < n) p <<= 1;
+    return p;
+}
+
 constexpr int RFW_CAP = 8192;  // k_refine_wide: rows scored per query (fp64 score + id in LDS)
 // k_refine_wide's phase A takes between KA and this many keys (the two-phase state holds as many):
 // up to 1.5 KA, within KA's power of two (the phase-A sort's size stays what KA alone gives)
@@ -407,9 +417,7 @@ struct RefineArgs {
 // any count of the best keys in [Kp, refine_kp2(Kp)], which ends the bisection early
 inline int refine_kp2(int Kp) {
     const int want = std::max(Kp, std::min(KP_MAX, Kp + Kp / 2));
-    int p = 1;
-    while (p < want) p <<= 1;
-    return p;
+    return (int)pow2_at_least(want, 1);
 }
 // workgroups per query of k_refine for a Kp-deep refine of nq queries (1 = no split)
 int refine_split(int nq, int Kp, int dt, int num_cu);
@@ -438,6 +446,8 @@ struct FullScanArgs {
     int G;                  // workgroups (row ranges)
     int all_queries;        // 1: scan every query of the block (cert is only written), no memset first
 };
+constexpr int FS_THREADS = 512;  // threads of a scan workgroup
+constexpr int FS_B = 512;        // candidate batch merged into a workgroup's list at once; also the most workgroups (G)
 size_t full_scan_scratch_bytes(int nq, int G, int k);
 void set_lds_attr(const void* fn, int bytes);  // max dynamic LDS of a kernel, set once per device
 hipError_t launch_full_scan(const FullScanArgs& a, hipStream_t st);

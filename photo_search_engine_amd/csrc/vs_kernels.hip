@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "vs_device.h"
+#include "vs_dispatch.h"
 
 namespace vs {
 
@@ -2065,20 +2066,20 @@ __global__ void __launch_bounds__(256) k_merge_shards(int metric, const double* 
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-#define VS_DISPATCH_DT(dt, KERNEL, ...)                                       \
-    do {                                                                      \
-        if ((dt) == DT_F32) hipLaunchKernelGGL(KERNEL<DT_F32>, __VA_ARGS__);  \
-        else if ((dt) == DT_BF16) hipLaunchKernelGGL(KERNEL<DT_BF16>, __VA_ARGS__); \
-        else hipLaunchKernelGGL(KERNEL<DT_F16>, __VA_ARGS__);                 \
-    } while (0)
+// one launch of a kernel templated on the dtype alone, 256 threads a workgroup: pick(dt) names it
+template <class PICK, class... ARGS>
+static hipError_t launch_by_dt(int dt, PICK&& pick, dim3 grid, hipStream_t st, const ARGS&... args) {
+    const bool known = with_dt(dt, [&](auto dt_c) { launch_kernel(pick(dt_c), 0, grid, dim3(256), 0, st, args...); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
+}
 
 static inline unsigned blocks4(int64_t n) { return (unsigned)((n + 3) / 4); }
 
 hipError_t launch_pack_rows(int dt, const float* src, int64_t n, int d, int dpad, uint8_t* data, int64_t lrow0,
                             float* sqn, unsigned* maxsq, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    VS_DISPATCH_DT(dt, k_pack_rows, dim3(blocks4(n)), dim3(256), 0, st, src, n, d, dpad, data, lrow0, sqn, maxsq);
-    return hipGetLastError();
+    return launch_by_dt(dt, [](auto c) { return k_pack_rows<c>; }, dim3(blocks4(n)), st, src, n, d, dpad, data, lrow0,
+                        sqn, maxsq);
 }
 
 hipError_t launch_synth_rows(int dt, uint64_t seed, int64_t grow0, int64_t n, int d, int dpad, uint8_t* data,
@@ -2092,9 +2093,8 @@ hipError_t launch_synth_rows(int dt, uint64_t seed, int64_t grow0, int64_t n, in
     const int64_t CHUNK = 1 << 22;  // rows per launch (grid-size bound)
     for (int64_t r0 = 0; r0 < n; r0 += CHUNK) {
         const int64_t m = n - r0 < CHUNK ? n - r0 : CHUNK;
-        VS_DISPATCH_DT(dt, k_synth_rows, dim3(blocks4(m)), dim3(256), 0, st, base, grow0 + r0, m, d, dpad, data,
-                       lrow0 + r0, normalize, sqn, maxsq);
-        hipError_t e = hipGetLastError();
+        const hipError_t e = launch_by_dt(dt, [](auto c) { return k_synth_rows<c>; }, dim3(blocks4(m)), st, base,
+                                          grow0 + r0, m, d, dpad, data, lrow0 + r0, normalize, sqn, maxsq);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -2110,39 +2110,29 @@ static inline uint64_t host_splitmix64(uint64_t x) {
 hipError_t launch_synth_f32(int dt, uint64_t seed, int64_t grow0, int64_t n, int d, int normalize, float* out,
                             hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    VS_DISPATCH_DT(dt, k_synth_f32, dim3(blocks4(n)), dim3(256), 0, st, host_splitmix64(seed), grow0, n, d, normalize,
-                   out);
-    return hipGetLastError();
+    return launch_by_dt(dt, [](auto c) { return k_synth_f32<c>; }, dim3(blocks4(n)), st, host_splitmix64(seed), grow0,
+                        n, d, normalize, out);
 }
 
 hipError_t launch_unpack_rows(int dt, const uint8_t* data, int64_t lrow0, int64_t n, int d, int dpad, float* out,
                               hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    VS_DISPATCH_DT(dt, k_unpack_rows, dim3(blocks4(n)), dim3(256), 0, st, data, lrow0, n, d, dpad, out);
-    return hipGetLastError();
+    return launch_by_dt(dt, [](auto c) { return k_unpack_rows<c>; }, dim3(blocks4(n)), st, data, lrow0, n, d, dpad,
+                        out);
 }
 
 hipError_t launch_gather_rows(int dt, const uint8_t* data, const int64_t* ids, int64_t n, int d, int dpad,
                               float* out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    VS_DISPATCH_DT(dt, k_gather_rows, dim3(blocks4(n)), dim3(256), 0, st, data, ids, n, d, dpad, out);
-    return hipGetLastError();
+    return launch_by_dt(dt, [](auto c) { return k_gather_rows<c>; }, dim3(blocks4(n)), st, data, ids, n, d, dpad, out);
 }
 
 hipError_t launch_pack_qtile(int dt, const float* q, int nqb, int d, int dpad, uint8_t* qt, float* qinfo, int* gcnt,
                              u64* drop, hipStream_t st, int* fails, const int* gate, const int* qidx, int* gcnt2,
                              u64* drop2) {
     if ((gcnt2 == nullptr) != (drop2 == nullptr)) return hipErrorInvalidValue;
-    if (dt == DT_F32)
-        hipLaunchKernelGGL(k_pack_qtile<DT_F32>, dim3(MFMA_QB / 4), dim3(256), 0, st, q, nqb, d, dpad, qt, qinfo,
-                           gcnt, drop, fails, gate, qidx, gcnt2, drop2);
-    else if (dt == DT_BF16)
-        hipLaunchKernelGGL(k_pack_qtile<DT_BF16>, dim3(MFMA_QB / 4), dim3(256), 0, st, q, nqb, d, dpad, qt, qinfo,
-                           gcnt, drop, fails, gate, qidx, gcnt2, drop2);
-    else
-        hipLaunchKernelGGL(k_pack_qtile<DT_F16>, dim3(MFMA_QB / 4), dim3(256), 0, st, q, nqb, d, dpad, qt, qinfo,
-                           gcnt, drop, fails, gate, qidx, gcnt2, drop2);
-    return hipGetLastError();
+    return launch_by_dt(dt, [](auto c) { return k_pack_qtile<c>; }, dim3(MFMA_QB / 4), st, q, nqb, d, dpad, qt, qinfo,
+                        gcnt, drop, fails, gate, qidx, gcnt2, drop2);
 }
 
 hipError_t launch_pack_qtile_split(int dt, const float* q, const int* qidx, const int* sinfo, int ntiles, int d,
@@ -2167,8 +2157,8 @@ hipError_t launch_pack_qtile_split(int dt, const float* q, const int* qidx, cons
 hipError_t launch_group_means(int dt, const uint8_t* data, int dpad, int d, int64_t g0, int64_t ng, int64_t n_rows,
                               int dpad8, uint16_t* gmean, unsigned* maxes, hipStream_t st) {
     if (ng <= 0) return hipSuccess;
-    VS_DISPATCH_DT(dt, k_group_means, dim3((unsigned)ng), dim3(256), 0, st, data, dpad, d, g0, n_rows, dpad8, gmean, maxes);
-    return hipGetLastError();
+    return launch_by_dt(dt, [](auto c) { return k_group_means<c>; }, dim3((unsigned)ng), st, data, dpad, d, g0, n_rows,
+                        dpad8, gmean, maxes);
 }
 
 hipError_t launch_group_dots(const uint16_t* gmean, int64_t ngroups, int dpad8, const float* q, int nq, int d, float* T,
@@ -2186,9 +2176,8 @@ hipError_t launch_quant_rows(int dt, const uint8_t* data, int dpad, int64_t r0, 
     const int64_t CHUNK = 1 << 22;  // rows per launch (grid-size bound)
     for (int64_t c0 = 0; c0 < n; c0 += CHUNK) {
         const int64_t m = n - c0 < CHUNK ? n - c0 : CHUNK;
-        VS_DISPATCH_DT(dt, k_quant_rows, dim3(blocks4(m)), dim3(256), 0, st, data, dpad, r0 + c0, m, d, data8, dpad8,
-                       rsb, maxes, gmean);
-        hipError_t e = hipGetLastError();
+        const hipError_t e = launch_by_dt(dt, [](auto c) { return k_quant_rows<c>; }, dim3(blocks4(m)), st, data, dpad,
+                                          r0 + c0, m, d, data8, dpad8, rsb, maxes, gmean);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -2401,11 +2390,12 @@ static void launch_gemv_dt(const ScreenArgs& a, const float* qp, int nqb, int nq
 hipError_t launch_screen_gemv(int dt, const ScreenArgs& a, const float* qp, int nqb, int nqpad, hipStream_t st) {
     if (dt == DT_I8 && (!a.rsb || !a.qinfo || (a.metric == METRIC_L2 && !a.sqn))) return hipErrorInvalidValue;
     if (a.gemv_split != 0 && a.gemv_split != 1 && a.gemv_split != GEMV_SPLIT) return hipErrorInvalidValue;
-    if (dt == DT_F32) launch_gemv_dt<DT_F32>(a, qp, nqb, nqpad, st);
-    else if (dt == DT_BF16) launch_gemv_dt<DT_BF16>(a, qp, nqb, nqpad, st);
-    else if (dt == DT_I8) launch_gemv_dt<DT_I8>(a, qp, nqb, nqpad, st);
-    else launch_gemv_dt<DT_F16>(a, qp, nqb, nqpad, st);
-    return hipGetLastError();
+    if (dt == DT_I8) {  // (the int8 screen copy: internal, no dtype of with_dt)
+        launch_gemv_dt<DT_I8>(a, qp, nqb, nqpad, st);
+        return hipGetLastError();
+    }
+    const bool known = with_dt(dt, [&](auto dt_c) { launch_gemv_dt<dt_c>(a, qp, nqb, nqpad, st); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_merge(const u64* in, int nseg, int qstride, int nq, int Kp, u64* out, int* nseg_out,
@@ -2418,18 +2408,6 @@ hipError_t launch_merge(const u64* in, int nseg, int qstride, int nq, int Kp, u6
     else hipLaunchKernelGGL(k_merge<16>, dim3(nb, nq), dim3(256), 0, st, in, nseg, qstride, nq, Kp, spb, out);
     *nseg_out = nb;
     return hipGetLastError();
-}
-
-template <int DT, int METRIC, bool QLDS>
-static void launch_refine_one(const RefineArgs& a, int nq, int KP2, size_t lds, hipStream_t st) {
-    set_lds_attr((const void*)k_refine<DT, METRIC, QLDS>, 152 * 1024);
-    set_lds_attr((const void*)k_refine_redo<DT, METRIC, QLDS>, 152 * 1024);
-    if (a.redo) {
-        hipLaunchKernelGGL((k_refine_redo<DT, METRIC, QLDS>), dim3(nq), dim3(RF_THREADS), lds, st, a, KP2);
-        return;
-    }
-    const int ns = a.nsplit > 1 ? a.nsplit : 1;
-    hipLaunchKernelGGL((k_refine<DT, METRIC, QLDS>), dim3(nq, ns), dim3(RF_THREADS), lds, st, a, KP2);
 }
 
 // Split a few-query refine over several workgroups per query when its rows (Kp per query) would
@@ -2448,40 +2426,25 @@ int refine_split(int nq, int Kp, int dt, int num_cu) {
     return ns >= 2 ? ns : 1;
 }
 
-template <int DT>
-static void launch_refine_dt(const RefineArgs& a, int nq, int KP2, size_t lds, bool qlds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        if (qlds) launch_refine_one<DT, METRIC_IP, true>(a, nq, KP2, lds, st);
-        else launch_refine_one<DT, METRIC_IP, false>(a, nq, KP2, lds, st);
-    } else {
-        if (qlds) launch_refine_one<DT, METRIC_L2, true>(a, nq, KP2, lds, st);
-        else launch_refine_one<DT, METRIC_L2, false>(a, nq, KP2, lds, st);
-    }
-}
-
 hipError_t launch_refine(const RefineArgs& a, int nq, hipStream_t st) {
     if (a.redo && (!a.gate || !a.cert)) return hipErrorInvalidValue;
     if (a.nsplit > 1 && (a.redo || !a.gsc || !a.gids || !a.gdone)) return hipErrorInvalidValue;
     const int KP2 = refine_kp2(a.Kp);
     const size_t base = (size_t)KP2 * 12 + 8 + (size_t)KP2 * 8;  // scores, ids, (query), kept keys
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;    // fp64 query, transposed 8-element groups
-    const bool qlds = base + qbytes <= 148 * 1024;  // query as fp64 in LDS when it fits
+    const size_t qbytes = query_lds_bytes(a.d);             // fp64 query, transposed 8-element groups
+    const bool qlds = base + qbytes <= LDS_QUERY_BUDGET;    // query as fp64 in LDS when it fits
     const size_t lds = qlds ? base + qbytes : base;
-    if (a.dt == DT_F32) launch_refine_dt<DT_F32>(a, nq, KP2, lds, qlds, st);
-    else if (a.dt == DT_BF16) launch_refine_dt<DT_BF16>(a, nq, KP2, lds, qlds, st);
-    else launch_refine_dt<DT_F16>(a, nq, KP2, lds, qlds, st);
-    return hipGetLastError();
-}
-
-template <int DT, bool QLDS>
-static void launch_refine_wide_one(const RefineArgs& a, int nq, int KA, size_t lds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        set_lds_attr((const void*)k_refine_wide<DT, METRIC_IP, QLDS>, 152 * 1024);
-        hipLaunchKernelGGL((k_refine_wide<DT, METRIC_IP, QLDS>), dim3(nq), dim3(RF_THREADS), lds, st, a, KA);
-    } else {
-        set_lds_attr((const void*)k_refine_wide<DT, METRIC_L2, QLDS>, 152 * 1024);
-        hipLaunchKernelGGL((k_refine_wide<DT, METRIC_L2, QLDS>), dim3(nq), dim3(RF_THREADS), lds, st, a, KA);
-    }
+    const bool known = dispatch(a.dt, a.metric, qlds, [&](auto dt, auto metric, auto qlds_c) {
+        set_lds_attr((const void*)k_refine<dt, metric, qlds_c>, LDS_DYN_MAX);
+        set_lds_attr((const void*)k_refine_redo<dt, metric, qlds_c>, LDS_DYN_MAX);
+        if (a.redo) {
+            launch_kernel(k_refine_redo<dt, metric, qlds_c>, 0, dim3(nq), dim3(RF_THREADS), lds, st, a, KP2);
+            return;
+        }
+        const int ns = a.nsplit > 1 ? a.nsplit : 1;
+        launch_kernel(k_refine<dt, metric, qlds_c>, 0, dim3(nq, ns), dim3(RF_THREADS), lds, st, a, KP2);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_refine_wide(const RefineArgs& a, int nq, int KA, hipStream_t st) {
@@ -2490,20 +2453,13 @@ hipError_t launch_refine_wide(const RefineArgs& a, int nq, int KA, hipStream_t s
         KA <= 0 || 2 * KA > RFW_CAP || (a.redo && (!a.gate || !a.cert || a.phase != 0)))
         return hipErrorInvalidValue;
     const size_t base = (size_t)RFW_CAP * 12;
-    const size_t qbytes = (size_t)((a.d + 7) >> 3) * 64;
-    const bool qlds = base + qbytes <= 148 * 1024;
+    const size_t qbytes = query_lds_bytes(a.d);
+    const bool qlds = base + qbytes <= LDS_QUERY_BUDGET;
     const size_t lds = qlds ? base + qbytes : base;
-    if (a.dt == DT_F32) {
-        if (qlds) launch_refine_wide_one<DT_F32, true>(a, nq, KA, lds, st);
-        else launch_refine_wide_one<DT_F32, false>(a, nq, KA, lds, st);
-    } else if (a.dt == DT_BF16) {
-        if (qlds) launch_refine_wide_one<DT_BF16, true>(a, nq, KA, lds, st);
-        else launch_refine_wide_one<DT_BF16, false>(a, nq, KA, lds, st);
-    } else {
-        if (qlds) launch_refine_wide_one<DT_F16, true>(a, nq, KA, lds, st);
-        else launch_refine_wide_one<DT_F16, false>(a, nq, KA, lds, st);
-    }
-    return hipGetLastError();
+    const bool known = dispatch(a.dt, a.metric, qlds, [&](auto dt, auto metric, auto qlds_c) {
+        launch_kernel(k_refine_wide<dt, metric, qlds_c>, LDS_DYN_MAX, dim3(nq), dim3(RF_THREADS), lds, st, a, KA);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_seed_mfma(int dt, const ScreenArgs& a, const uint8_t* qt, int nqb, hipStream_t st) {
@@ -2527,9 +2483,8 @@ hipError_t launch_pack_rows_map(int dt, const float* src, int64_t n, int d, int 
                                 const int64_t* slots, float* sqn, unsigned* maxsq, uint32_t* slot_id, int64_t id0,
                                 hipStream_t st) {
     if (n <= 0) return hipSuccess;
-    VS_DISPATCH_DT(dt, k_pack_rows_map, dim3(blocks4(n)), dim3(256), 0, st, src, n, d, dpad, data, slots, sqn, maxsq,
-                   slot_id, id0);
-    return hipGetLastError();
+    return launch_by_dt(dt, [](auto c) { return k_pack_rows_map<c>; }, dim3(blocks4(n)), st, src, n, d, dpad, data,
+                        slots, sqn, maxsq, slot_id, id0);
 }
 
 hipError_t launch_round_f32(int dt, float* x, int64_t n, hipStream_t st) {
@@ -2540,22 +2495,19 @@ hipError_t launch_round_f32(int dt, float* x, int64_t n, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <int DT>
-static void launch_ivf_scan_dt(int nq_class, const IvfScanArgs& a, int grid, hipStream_t st) {
-    switch (nq_class) {
-        case 1: hipLaunchKernelGGL((k_ivf_scan<DT, 1>), dim3(grid), dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((k_ivf_scan<DT, 2>), dim3(grid), dim3(256), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((k_ivf_scan<DT, 4>), dim3(grid), dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL((k_ivf_scan<DT, IVF_QG>), dim3(grid), dim3(256), 0, st, a); break;
-    }
-}
 hipError_t launch_ivf_scan(int dt, int nq_class, const IvfScanArgs& a, int grid, hipStream_t st) {
     if (a.n_items <= 0 || grid <= 0) return hipSuccess;
     if (nq_class != 1 && nq_class != 2 && nq_class != 4 && nq_class != IVF_QG) return hipErrorInvalidValue;
-    if (dt == DT_F32) launch_ivf_scan_dt<DT_F32>(nq_class, a, grid, st);
-    else if (dt == DT_BF16) launch_ivf_scan_dt<DT_BF16>(nq_class, a, grid, st);
-    else launch_ivf_scan_dt<DT_F16>(nq_class, a, grid, st);
-    return hipGetLastError();
+    const bool known = with_dt(dt, [&](auto dt_c) {
+        auto launch = [&](auto kernel) { launch_kernel(kernel, 0, dim3(grid), dim3(256), 0, st, a); };
+        switch (nq_class) {
+            case 1: launch(k_ivf_scan<dt_c, 1>); break;
+            case 2: launch(k_ivf_scan<dt_c, 2>); break;
+            case 4: launch(k_ivf_scan<dt_c, 4>); break;
+            default: launch(k_ivf_scan<dt_c, IVF_QG>); break;
+        }
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_ivf_scan_dyn(int dt, const IvfScanArgs& a, int grid, hipStream_t st) {
@@ -2564,16 +2516,13 @@ hipError_t launch_ivf_scan_dyn(int dt, const IvfScanArgs& a, int grid, hipStream
     // the queries in LDS when an item's IVF_QG of them fit 48 KiB (3 resident workgroups per CU, as
     // the VGPR budget allows; d <= 1536)
     const size_t ql = (size_t)IVF_QG * a.dpad * 4;
-    if (ql <= 48 * 1024) {
-        if (dt == DT_F32) hipLaunchKernelGGL((k_ivf_scan_dyn<DT_F32, true>), dim3(grid), dim3(256), ql, st, a);
-        else if (dt == DT_BF16) hipLaunchKernelGGL((k_ivf_scan_dyn<DT_BF16, true>), dim3(grid), dim3(256), ql, st, a);
-        else hipLaunchKernelGGL((k_ivf_scan_dyn<DT_F16, true>), dim3(grid), dim3(256), ql, st, a);
-        return hipGetLastError();
-    }
-    if (dt == DT_F32) hipLaunchKernelGGL((k_ivf_scan_dyn<DT_F32, false>), dim3(grid), dim3(256), 0, st, a);
-    else if (dt == DT_BF16) hipLaunchKernelGGL((k_ivf_scan_dyn<DT_BF16, false>), dim3(grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_ivf_scan_dyn<DT_F16, false>), dim3(grid), dim3(256), 0, st, a);
-    return hipGetLastError();
+    const bool qlds = ql <= 48 * 1024;
+    const bool known = with_dt(dt, [&](auto dt_c) {
+        with_bool(qlds, [&](auto qlds_c) {
+            launch_kernel(k_ivf_scan_dyn<dt_c, qlds_c>, 0, dim3(grid), dim3(256), qlds_c ? ql : 0, st, a);
+        });
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_merge_shards(int metric, const double* S_in, const int64_t* I_in, int G, int64_t nq, int k,
@@ -2617,7 +2566,7 @@ struct HnLds {
 __host__ __device__ inline size_t hn_layout(int d, int k, int ef, int nbmax, bool qlds, uint8_t* base, HnLds* L) {
     size_t off = 0;
     uint8_t* p[16];
-    const size_t sz[16] = {qlds ? (size_t)((d + 7) >> 3) * 64 : 0,
+    const size_t sz[16] = {qlds ? query_lds_bytes(d) : 0,
                            (size_t)ef * 8, (size_t)ef * 8, (size_t)ef * 4, (size_t)ef * 4, (size_t)ef * 4, (size_t)ef * 4,
                            (size_t)k * 8, (size_t)k * 8, (size_t)k * 4, (size_t)k * 4,
                            (size_t)nbmax * 8, (size_t)nbmax * 4, (size_t)nbmax * 8, (size_t)nbmax * 4,
@@ -2908,32 +2857,16 @@ __global__ void __launch_bounds__(HN_SEARCH_THREADS) k_hnsw_search(HnswArgs a) {
     }
 }
 
-template <int DT, int METRIC, bool QLDS>
-static void launch_hnsw_one(const HnswArgs& a, int nq, size_t lds, hipStream_t st) {
-    set_lds_attr((const void*)k_hnsw_search<DT, METRIC, QLDS>, (int)HN_LDS_CAP);
-    hipLaunchKernelGGL((k_hnsw_search<DT, METRIC, QLDS>), dim3(nq), dim3(HN_SEARCH_THREADS), lds, st, a);
-}
-template <int DT>
-static void launch_hnsw_dt(const HnswArgs& a, int nq, size_t lds, bool qlds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        if (qlds) launch_hnsw_one<DT, METRIC_IP, true>(a, nq, lds, st);
-        else launch_hnsw_one<DT, METRIC_IP, false>(a, nq, lds, st);
-    } else {
-        if (qlds) launch_hnsw_one<DT, METRIC_L2, true>(a, nq, lds, st);
-        else launch_hnsw_one<DT, METRIC_L2, false>(a, nq, lds, st);
-    }
-}
 hipError_t launch_hnsw_search(const HnswArgs& a, int nq, hipStream_t st) {
     if (nq <= 0) return hipSuccess;
     if (a.k < 1 || a.ef < a.k || a.ef > HN_EF_MAX || a.nbmax > HN_NB_MAX || a.nbmax < 1) return hipErrorInvalidValue;
     const size_t lds = hnsw_lds_bytes(a.d, a.k, a.ef, a.nbmax);
     if (lds > HN_LDS_CAP) return hipErrorInvalidValue;
     const bool qlds = hn_layout(a.d, a.k, a.ef, a.nbmax, true, nullptr, nullptr) <= HN_LDS_CAP;
-    if (a.dt == DT_F32) launch_hnsw_dt<DT_F32>(a, nq, lds, qlds, st);
-    else if (a.dt == DT_BF16) launch_hnsw_dt<DT_BF16>(a, nq, lds, qlds, st);
-    else if (a.dt == DT_F16) launch_hnsw_dt<DT_F16>(a, nq, lds, qlds, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const bool known = dispatch(a.dt, a.metric, qlds, [&](auto dt, auto metric, auto qlds_c) {
+        launch_kernel(k_hnsw_search<dt, metric, qlds_c>, (int)HN_LDS_CAP, dim3(nq), dim3(HN_SEARCH_THREADS), lds, st, a);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2947,7 +2880,7 @@ hipError_t launch_hnsw_search(const HnswArgs& a, int nq, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 __host__ __device__ inline size_t hp_layout(int d, int C, int W, uint8_t* base, double** qs, double** cd, int** ci,
                                             double** sd, int** si, int** kept) {
-    const size_t sz[6] = {(size_t)((d + 7) >> 3) * 64, (size_t)C * 8, (size_t)C * 4, (size_t)C * 8, (size_t)C * 4,
+    const size_t sz[6] = {query_lds_bytes(d), (size_t)C * 8, (size_t)C * 4, (size_t)C * 8, (size_t)C * 4,
                           (size_t)W * 4};
     uint8_t* p[6];
     size_t off = 0;
@@ -3070,26 +3003,15 @@ __global__ void __launch_bounds__(HN_THREADS) k_hnsw_prune(HnswPruneArgs a) {
     for (int j = tid; j < a.W; j += HN_THREADS) out[j] = j < nk ? kept[j] : -1;
 }
 
-template <int DT>
-static void launch_prune_dt(const HnswPruneArgs& a, int m, size_t lds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        set_lds_attr((const void*)k_hnsw_prune<DT, METRIC_IP>, (int)HN_LDS_CAP);
-        hipLaunchKernelGGL((k_hnsw_prune<DT, METRIC_IP>), dim3(m), dim3(HN_THREADS), lds, st, a);
-    } else {
-        set_lds_attr((const void*)k_hnsw_prune<DT, METRIC_L2>, (int)HN_LDS_CAP);
-        hipLaunchKernelGGL((k_hnsw_prune<DT, METRIC_L2>), dim3(m), dim3(HN_THREADS), lds, st, a);
-    }
-}
 hipError_t launch_hnsw_prune(const HnswPruneArgs& a, int m, hipStream_t st) {
     if (m <= 0) return hipSuccess;
     if (a.C < 1 || a.C > HP_C_MAX || a.W < 1 || a.W > HN_NB_MAX) return hipErrorInvalidValue;
     const size_t lds = hnsw_prune_lds_bytes(a.d, a.C, a.W);
     if (lds > HN_LDS_CAP) return hipErrorInvalidValue;
-    if (a.dt == DT_F32) launch_prune_dt<DT_F32>(a, m, lds, st);
-    else if (a.dt == DT_BF16) launch_prune_dt<DT_BF16>(a, m, lds, st);
-    else if (a.dt == DT_F16) launch_prune_dt<DT_F16>(a, m, lds, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const bool known = dispatch(a.dt, a.metric, [&](auto dt, auto metric) {
+        launch_kernel(k_hnsw_prune<dt, metric>, (int)HN_LDS_CAP, dim3(m), dim3(HN_THREADS), lds, st, a);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vs

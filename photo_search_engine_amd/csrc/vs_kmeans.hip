@@ -23,6 +23,7 @@
 // stores only.
 #include "vs_index.h"
 #include "vs_device.h"
+#include "vs_dispatch.h"
 
 using namespace vs;
 
@@ -313,13 +314,10 @@ hipError_t launch_km_segsum(int dt, const uint8_t* data, int d, int dpad, const 
     const int64_t blocks = (nseg * ngroups + KM_NW - 1) / KM_NW;
     if (blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
     const dim3 g((unsigned)blocks), b(KM_THREADS);
-    if (dt == DT_F32) hipLaunchKernelGGL(k_km_segsum<DT_F32>, g, b, 0, st, data, d, dpad, mem, order, seg, nseg, ngroups, m, n_valid, P);
-    else if (dt == DT_BF16)
-        hipLaunchKernelGGL(k_km_segsum<DT_BF16>, g, b, 0, st, data, d, dpad, mem, order, seg, nseg, ngroups, m, n_valid, P);
-    else if (dt == DT_F16)
-        hipLaunchKernelGGL(k_km_segsum<DT_F16>, g, b, 0, st, data, d, dpad, mem, order, seg, nseg, ngroups, m, n_valid, P);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const bool known = with_dt(dt, [&](auto dt_c) {
+        launch_kernel(k_km_segsum<dt_c>, 0, g, b, 0, st, data, d, dpad, mem, order, seg, nseg, ngroups, m, n_valid, P);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_km_finalize(const double* P, const int64_t* segoff, const unsigned* counts, int k, int d, float* cen,

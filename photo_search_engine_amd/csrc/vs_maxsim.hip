@@ -35,7 +35,7 @@ namespace vs {
 
 constexpr int MS_THREADS = 512;  // k_maxsim_walk, k_maxsim_rank: one workgroup per query
 constexpr int MS_NW = MS_THREADS / 64;
-constexpr size_t MS_SCAN_QLDS = 148 * 1024;  // the scan stages the sub-queries as fp64 in LDS up to this size
+constexpr size_t MS_SCAN_QLDS = LDS_QUERY_BUDGET;  // the scan stages the sub-queries as fp64 in LDS up to this size
 static_assert(FUSE_WALK_MAX <= 32 * MS_THREADS, "the duplicate mask keeps one bit per entry of a thread");
 static_assert(FUSE_MAX_Q <= MS_NW, "the certificate rescoring gives every list's last entry a wave");
 
@@ -307,29 +307,10 @@ __global__ void __launch_bounds__(MS_THREADS) k_maxsim_walk(MaxsimWalkArgs a, in
 }
 
 size_t maxsim_walk_lds(int64_t n_entries, int d, int m, bool* qlds) {
-    size_t n2 = 64;
-    while ((int64_t)n2 < n_entries) n2 <<= 1;
-    const size_t base = n2 * 12, qbytes = (size_t)m * ((d + 7) >> 3) * 64;
+    const size_t base = pow2_at_least(n_entries, 64) * 12, qbytes = (size_t)m * query_lds_bytes(d);
     const bool fits = base + qbytes <= FUSE_DYN_CAP;
     if (qlds) *qlds = fits;
     return fits ? base + qbytes : base;
-}
-
-template <int DT, int METRIC, bool QLDS>
-static void launch_maxsim_walk_one(const MaxsimWalkArgs& a, int nq, int n2, size_t lds, hipStream_t st) {
-    set_lds_attr((const void*)k_maxsim_walk<DT, METRIC, QLDS>, (int)FUSE_DYN_CAP);
-    hipLaunchKernelGGL((k_maxsim_walk<DT, METRIC, QLDS>), dim3(nq), dim3(MS_THREADS), lds, st, a, n2);
-}
-
-template <int DT>
-static void launch_maxsim_walk_dt(const MaxsimWalkArgs& a, int nq, int n2, size_t lds, bool qlds, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        if (qlds) launch_maxsim_walk_one<DT, METRIC_IP, true>(a, nq, n2, lds, st);
-        else launch_maxsim_walk_one<DT, METRIC_IP, false>(a, nq, n2, lds, st);
-    } else {
-        if (qlds) launch_maxsim_walk_one<DT, METRIC_L2, true>(a, nq, n2, lds, st);
-        else launch_maxsim_walk_one<DT, METRIC_L2, false>(a, nq, n2, lds, st);
-    }
 }
 
 hipError_t launch_maxsim_walk(const MaxsimWalkArgs& a, int nq, hipStream_t st) {
@@ -345,13 +326,11 @@ hipError_t launch_maxsim_walk(const MaxsimWalkArgs& a, int nq, hipStream_t st) {
     bool qlds;
     const size_t lds = maxsim_walk_lds(n, a.d, a.m, &qlds);
     if (lds > FUSE_DYN_CAP) return hipErrorInvalidValue;
-    int n2 = 64;
-    while (n2 < n) n2 <<= 1;
-    if (a.dt == DT_F32) launch_maxsim_walk_dt<DT_F32>(a, nq, n2, lds, qlds, st);
-    else if (a.dt == DT_BF16) launch_maxsim_walk_dt<DT_BF16>(a, nq, n2, lds, qlds, st);
-    else if (a.dt == DT_F16) launch_maxsim_walk_dt<DT_F16>(a, nq, n2, lds, qlds, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const int n2 = (int)pow2_at_least(n, 64);
+    const bool known = dispatch(a.dt, a.metric, qlds, [&](auto dt, auto metric, auto qlds_c) {
+        launch_kernel(k_maxsim_walk<dt, metric, qlds_c>, (int)FUSE_DYN_CAP, dim3(nq), dim3(MS_THREADS), lds, st, a, n2);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ---- the scan ------------------------------------------------------------------------------------
@@ -423,47 +402,21 @@ __global__ void __launch_bounds__(FS_THREADS) k_maxsim_scan(MaxsimScanArgs a, co
     }
 }
 
-template <int DT, int METRIC>
-static void launch_maxsim_scan_m(const MaxsimScanArgs& a, const uint32_t* ids, int64_t n_ids, int G, int qy, bool qlds,
-                                 size_t lds, hipStream_t st) {
-    const dim3 grid(G, qy), block(FS_THREADS);
-    if (ids) {
-        if (qlds) {
-            set_lds_attr((const void*)k_maxsim_scan<DT, METRIC, true, true>, 152 * 1024);
-            hipLaunchKernelGGL((k_maxsim_scan<DT, METRIC, true, true>), grid, block, lds, st, a, ids, n_ids);
-        } else {
-            hipLaunchKernelGGL((k_maxsim_scan<DT, METRIC, false, true>), grid, block, 0, st, a, ids, n_ids);
-        }
-    } else {
-        if (qlds) {
-            set_lds_attr((const void*)k_maxsim_scan<DT, METRIC, true, false>, 152 * 1024);
-            hipLaunchKernelGGL((k_maxsim_scan<DT, METRIC, true, false>), grid, block, lds, st, a, ids, n_ids);
-        } else {
-            hipLaunchKernelGGL((k_maxsim_scan<DT, METRIC, false, false>), grid, block, 0, st, a, ids, n_ids);
-        }
-    }
-}
-
-template <int DT>
-static void launch_maxsim_scan_dt(const MaxsimScanArgs& a, const uint32_t* ids, int64_t n_ids, int G, int qy, bool qlds,
-                                  size_t lds, hipStream_t st) {
-    if (a.metric == METRIC_IP) launch_maxsim_scan_m<DT, METRIC_IP>(a, ids, n_ids, G, qy, qlds, lds, st);
-    else launch_maxsim_scan_m<DT, METRIC_L2>(a, ids, n_ids, G, qy, qlds, lds, st);
-}
-
 hipError_t launch_maxsim_scan(const MaxsimScanArgs& a, const uint32_t* ids, int64_t n_ids, int G, int qy, hipStream_t st) {
     if (a.nq <= 0) return hipSuccess;
     if (qy < 1 || qy > a.nq || qy > 65535 || G < 1 || a.m < 1 || a.m > FUSE_MAX_Q || a.d < 1 || !a.corpus || !a.q ||
         !a.table || !a.g.gid || a.g.n_cov < 1 || a.g.n_cov > 0xFFFFFFFFll || a.g.ncodes < 1 || a.g.G < 0 ||
         (ids && n_ids <= 0) || (a.metric != METRIC_IP && a.metric != METRIC_L2))
         return hipErrorInvalidValue;
-    const size_t qbytes = (size_t)a.m * ((a.d + 7) >> 3) * 64;
+    const size_t qbytes = (size_t)a.m * query_lds_bytes(a.d);
     const bool qlds = qbytes <= MS_SCAN_QLDS;
-    if (a.dt == DT_F32) launch_maxsim_scan_dt<DT_F32>(a, ids, n_ids, G, qy, qlds, qbytes, st);
-    else if (a.dt == DT_BF16) launch_maxsim_scan_dt<DT_BF16>(a, ids, n_ids, G, qy, qlds, qbytes, st);
-    else if (a.dt == DT_F16) launch_maxsim_scan_dt<DT_F16>(a, ids, n_ids, G, qy, qlds, qbytes, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    const dim3 grid(G, qy), block(FS_THREADS);
+    // (the sub-queries in global memory: no dynamic LDS, and the default limit serves)
+    const bool known = dispatch(a.dt, a.metric, qlds, ids != nullptr, [&](auto dt, auto metric, auto qlds_c, auto sel) {
+        launch_kernel(k_maxsim_scan<dt, metric, qlds_c, sel>, qlds_c ? LDS_DYN_MAX : 0, grid, block, qlds_c ? qbytes : 0, st,
+                      a, ids, n_ids);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ---- the rank ------------------------------------------------------------------------------------
@@ -532,14 +485,12 @@ hipError_t launch_maxsim_rank(const unsigned long long* table, int nq, int m, in
     if (!table || !cand || m < 1 || m > FUSE_MAX_Q || ncodes < 1 || ncodes > 0xFFFFFFFEll || k < 1 || k > K_MAX ||
         (metric != METRIC_IP && metric != METRIC_L2))
         return hipErrorInvalidValue;
-    int n2 = 1024;
-    while (n2 < k + MS_THREADS) n2 <<= 1;
+    const int n2 = (int)pow2_at_least(k + MS_THREADS, 1024);
     const size_t lds = (size_t)n2 * 12;
-    if (metric == METRIC_IP)
-        hipLaunchKernelGGL((k_maxsim_rank<METRIC_IP>), dim3(nq), dim3(MS_THREADS), lds, st, table, m, ncodes, k, n2, cand);
-    else
-        hipLaunchKernelGGL((k_maxsim_rank<METRIC_L2>), dim3(nq), dim3(MS_THREADS), lds, st, table, m, ncodes, k, n2, cand);
-    return hipGetLastError();
+    const bool known = with_metric(metric, [&](auto metric_c) {
+        launch_kernel(k_maxsim_rank<metric_c>, 0, dim3(nq), dim3(MS_THREADS), lds, st, table, m, ncodes, k, n2, cand);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vs

@@ -142,9 +142,10 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_emit(RangeEmitArgs a) {
 
 hipError_t launch_range_emit(const RangeEmitArgs& a, int nq, hipStream_t st) {
     if (nq <= 0 || !a.seg || !a.D || !a.I || !a.S || !a.psc[0] || !a.pid[0]) return hipErrorInvalidValue;
-    if (a.metric == METRIC_IP) hipLaunchKernelGGL(k_range_emit<METRIC_IP>, dim3(nq), dim3(FS_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(k_range_emit<METRIC_L2>, dim3(nq), dim3(FS_THREADS), 0, st, a);
-    return hipGetLastError();
+    const bool known = with_metric(a.metric, [&](auto metric) {
+        launch_kernel(k_range_emit<metric>, 0, dim3(nq), dim3(FS_THREADS), 0, st, a);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vs

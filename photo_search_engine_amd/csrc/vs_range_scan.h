@@ -476,7 +476,7 @@ __global__ void __launch_bounds__(FS_THREADS) k_range_refine(RangeArgs a, const 
 
 // the staged query's bytes of dynamic LDS; 0: the query is too long and stays in global memory (QLDS false)
 inline size_t rs_query_lds(int d) {
-    const size_t qbytes = (size_t)((d + 7) >> 3) * 64;
+    const size_t qbytes = query_lds_bytes(d);
     return qbytes <= RS_QLDS_MAX ? qbytes : 0;
 }
 
@@ -485,45 +485,17 @@ inline bool rs_args_ok(const RangeArgs& a) {
            (a.metric == METRIC_IP || a.metric == METRIC_L2) && a.row0 >= 0 && a.row0 < a.n_valid;
 }
 
-// fn(dt, metric, qlds), the three as integral constants, for the block's dtype, metric and query length;
-// false: the dtype has no kernel (F32: whether fp32 rows have one -- the screen, hence the refine, has none)
-template <bool F32, class FN>
-bool rs_dispatch(const RangeArgs& a, FN&& fn) {
-    const bool qlds = rs_query_lds(a.d) != 0;
-    auto with_dt = [&](auto dt) {
-        auto with_metric = [&](auto metric) {
-            if (qlds) fn(dt, metric, std::true_type{});
-            else fn(dt, metric, std::false_type{});
-        };
-        if (a.metric == METRIC_IP) with_metric(std::integral_constant<int, METRIC_IP>{});
-        else with_metric(std::integral_constant<int, METRIC_L2>{});
-        return true;
-    };
-    if constexpr (F32) {
-        if (a.dt == DT_F32) return with_dt(std::integral_constant<int, DT_F32>{});
-    }
-    if (a.dt == DT_BF16) return with_dt(std::integral_constant<int, DT_BF16>{});
-    if (a.dt == DT_F16) return with_dt(std::integral_constant<int, DT_F16>{});
-    return false;
-}
-
 template <class SINK, bool SELF>
 hipError_t rs_launch_scan(const RangeArgs& a, const typename SINK::Args& sa, size_t sink_lds, int lds_attr, int G, int qy,
                           const uint32_t* ids, int64_t m, hipStream_t st) {
     if (!rs_args_ok(a) || G < 1 || qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (ids && m == 0) || (!ids && m != 0) ||
         (ids && a.row0 != 0))
         return hipErrorInvalidValue;
-    const size_t lds = rs_query_lds(a.d) + sink_lds;
+    const size_t qbytes = rs_query_lds(a.d), lds = qbytes + sink_lds;
     const dim3 grid(G, qy), block(FS_THREADS);
-    auto launch = [&](auto kernel) {
-        if (lds_attr) set_lds_attr((const void*)kernel, lds_attr);
-        hipLaunchKernelGGL(kernel, grid, block, lds, st, a, ids, m, sa);
-    };
-    const bool known = rs_dispatch<true>(a, [&](auto dt, auto metric, auto qlds) {
-        constexpr int DT = decltype(dt)::value, METRIC = decltype(metric)::value;
-        constexpr bool QLDS = decltype(qlds)::value;
-        if (ids) launch(k_range_scan<DT, METRIC, QLDS, true, SELF, SINK>);
-        else launch(k_range_scan<DT, METRIC, QLDS, false, SELF, SINK>);
+    const bool known = dispatch(a.dt, a.metric, qbytes != 0, ids != nullptr, [&](auto dt, auto metric, auto qlds,
+                                auto sel) {
+        launch_kernel(k_range_scan<dt, metric, qlds, sel, SELF, SINK>, lds_attr, grid, block, lds, st, a, ids, m, sa);
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;
 }
@@ -534,10 +506,8 @@ hipError_t rs_launch_refine(const RangeArgs& a, const typename SINK::Args& sa, c
     if (!rs_args_ok(a) || !glist || !gcnt || lcap <= 0 || ny < 1 || ny > 65535) return hipErrorInvalidValue;
     const size_t lds = rs_query_lds(a.d);
     const dim3 grid(a.nq, ny), block(FS_THREADS);
-    const bool known = rs_dispatch<false>(a, [&](auto dt, auto metric, auto qlds) {
-        constexpr int DT = decltype(dt)::value, METRIC = decltype(metric)::value;
-        constexpr bool QLDS = decltype(qlds)::value;
-        hipLaunchKernelGGL((k_range_refine<DT, METRIC, QLDS, SELF, SINK>), grid, block, lds, st, a, glist, gcnt, lcap, sa);
+    const bool known = dispatch<false>(a.dt, a.metric, lds != 0, [&](auto dt, auto metric, auto qlds) {  // (no fp32 screen)
+        launch_kernel(k_range_refine<dt, metric, qlds, SELF, SINK>, 0, grid, block, lds, st, a, glist, gcnt, lcap, sa);
     });
     return known ? hipGetLastError() : hipErrorInvalidValue;
 }

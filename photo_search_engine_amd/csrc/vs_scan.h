@@ -15,12 +15,11 @@
 #include <type_traits>
 
 #include "vs_device.h"
+#include "vs_dispatch.h"
 
 namespace vs {
 
-constexpr int FS_THREADS = 512;
-constexpr int FS_NW = FS_THREADS / 64;
-constexpr int FS_B = 512;  // candidate batch merged into a workgroup's list at once (= FS_THREADS)
+constexpr int FS_NW = FS_THREADS / 64;  // (FS_THREADS, FS_B: vs_internal.h)
 static_assert(FS_B == FS_THREADS, "the batch sort keeps one element per thread");
 
 __device__ __forceinline__ bool fs_better(double sa, uint32_t ia, double sb, uint32_t ib) {
@@ -94,13 +93,12 @@ template <int DT>
 constexpr int fs_rows() { return DT == DT_F32 ? 4 : 8; }
 
 // dynamic LDS of one scan workgroup: two k-lists and the batch (KL = k's power of two, >= 64), and
-// the query as fp64 when it fits beside them (qlds)
-inline size_t fs_lds_bytes(int k, int d, int* KL_out, bool* qlds_out) {
-    int KL = 64;
-    while (KL < k) KL <<= 1;
+// the query -- a fused scan's m sub-queries -- as fp64 when it fits beside them (qlds)
+inline size_t fs_lds_bytes(int k, int d, int m, int* KL_out, bool* qlds_out) {
+    const int KL = (int)pow2_at_least(k, 64);
     const size_t base = (size_t)KL * 24 + (size_t)FS_B * 12;
-    const size_t qbytes = (size_t)((d + 7) >> 3) * 64;
-    const bool qlds = base + qbytes <= 148 * 1024;
+    const size_t qbytes = (size_t)m * query_lds_bytes(d);
+    const bool qlds = base + qbytes <= LDS_QUERY_BUDGET;
     *KL_out = KL;
     *qlds_out = qlds;
     return qlds ? base + qbytes : base;
@@ -349,6 +347,30 @@ __device__ __forceinline__ void fs_scan_body(const FullScanArgs& a, int KL, cons
             if (a.count) atomicAdd(a.count, 1u);
         }
     }
+}
+
+// ---- the launcher ------------------------------------------------------------------------------------
+// what every scan over fs_scan_body asks of its arguments
+inline bool fs_args_ok(const FullScanArgs& a) {
+    return a.nq > 0 && a.k > 0 && a.k <= KP_MAX && a.G > 0 && a.G <= FS_B && a.n_valid > 0 && a.cert && a.I && a.gsc &&
+           a.gid && a.gdone && a.q && a.corpus && (a.metric == METRIC_IP || a.metric == METRIC_L2);
+}
+
+// One launch of a scan kernel: the shared checks, the LDS rule (m: the sub-queries staged per query), the grid
+// a.G x ny and the dtype x metric x QLDS x SEL dispatch.  pick(dt, metric, qlds, sel) names the kernel; its
+// arguments are (a, KL, extra...).  What a scan adds stays in its own launch_*_scan: its own checks, ny and sel.
+template <class PICK, class... EXTRA>
+hipError_t fs_launch_scan(const FullScanArgs& a, int m, bool sel, int ny, hipStream_t st, PICK&& pick,
+                          const EXTRA&... extra) {
+    if (!fs_args_ok(a)) return hipErrorInvalidValue;
+    int KL;
+    bool qlds;
+    const size_t lds = fs_lds_bytes(a.k, a.d, m, &KL, &qlds);
+    const dim3 grid(a.G, ny), block(FS_THREADS);
+    const bool known = dispatch(a.dt, a.metric, qlds, sel, [&](auto dt, auto metric, auto qlds_c, auto sel_c) {
+        launch_kernel(pick(dt, metric, qlds_c, sel_c), LDS_DYN_MAX, grid, block, lds, st, a, KL, extra...);
+    });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace vs

@@ -70,7 +70,7 @@ namespace {
 constexpr int kSelScanRows = 64;  // list positions per workgroup, at least
 void sel_scan_block(vs_index* ix, Ctx* c, const vs_sel* sel, const float* q, int nqb, int k, const SearchOut& out,
                     hipStream_t st, bool all_queries) {
-    const FullScanArgs a = full_scan_args(ix, c, sel->m, kSelScanRows, std::min(ix->num_cu, 512 /* FS_B */), q, nqb, k,
+    const FullScanArgs a = full_scan_args(ix, c, sel->m, kSelScanRows, std::min(ix->num_cu, FS_B), q, nqb, k,
                                           out, all_queries, st);
     // a short list leaves CUs idle: deal the block's queries over as many slices as fill them
     const int qy = std::max(1, std::min(nqb, ix->num_cu / a.G));

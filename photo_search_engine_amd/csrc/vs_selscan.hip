@@ -142,38 +142,10 @@ __global__ void __launch_bounds__(FS_THREADS) k_sel_scan(FullScanArgs a, int KL,
     fs_scan_body<DT, METRIC, QLDS, true>(a, KL, ids, m);
 }
 
-template <int DT, int METRIC, bool QLDS>
-static void launch_sel_scan_one(const FullScanArgs& a, int KL, size_t lds, const uint32_t* ids, int64_t m, int qy,
-                                hipStream_t st) {
-    set_lds_attr((const void*)k_sel_scan<DT, METRIC, QLDS>, 152 * 1024);
-    hipLaunchKernelGGL((k_sel_scan<DT, METRIC, QLDS>), dim3(a.G, qy), dim3(FS_THREADS), lds, st, a, KL, ids, m);
-}
-
-template <int DT>
-static void launch_sel_scan_dt(const FullScanArgs& a, int KL, size_t lds, bool qlds, const uint32_t* ids, int64_t m,
-                               int qy, hipStream_t st) {
-    if (a.metric == METRIC_IP) {
-        if (qlds) launch_sel_scan_one<DT, METRIC_IP, true>(a, KL, lds, ids, m, qy, st);
-        else launch_sel_scan_one<DT, METRIC_IP, false>(a, KL, lds, ids, m, qy, st);
-    } else {
-        if (qlds) launch_sel_scan_one<DT, METRIC_L2, true>(a, KL, lds, ids, m, qy, st);
-        else launch_sel_scan_one<DT, METRIC_L2, false>(a, KL, lds, ids, m, qy, st);
-    }
-}
-
 hipError_t launch_sel_scan(const FullScanArgs& a, const uint32_t* ids, int64_t m, int qy, hipStream_t st) {
-    if (qy < 1 || qy > a.nq || qy > 65535) return hipErrorInvalidValue;
-    if (a.nq <= 0 || a.k <= 0 || a.k > KP_MAX || a.G <= 0 || a.G > FS_B || a.n_valid <= 0 || !a.cert || !a.I || !a.gsc ||
-        !a.gid || !a.gdone || !a.q || !a.corpus || m < 0 || (m > 0 && !ids))
-        return hipErrorInvalidValue;
-    int KL;
-    bool qlds;
-    const size_t lds = fs_lds_bytes(a.k, a.d, &KL, &qlds);
-    if (a.dt == DT_F32) launch_sel_scan_dt<DT_F32>(a, KL, lds, qlds, ids, m, qy, st);
-    else if (a.dt == DT_BF16) launch_sel_scan_dt<DT_BF16>(a, KL, lds, qlds, ids, m, qy, st);
-    else if (a.dt == DT_F16) launch_sel_scan_dt<DT_F16>(a, KL, lds, qlds, ids, m, qy, st);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (qy < 1 || qy > a.nq || qy > 65535 || m < 0 || (m > 0 && !ids)) return hipErrorInvalidValue;
+    return fs_launch_scan(a, 1, true, qy, st,
+                          [](auto dt, auto metric, auto qlds, auto) { return k_sel_scan<dt, metric, qlds>; }, ids, m);
 }
 
 // ---- the overfetch tier's filter ------------------------------------------------------------------
